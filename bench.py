@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — proofs/sec of the plonkathon prover hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment), or — when WORLD_SIZE is not set — bench.py spawns the
@@ -16,15 +16,25 @@ Proofs are independent, so N GPUs shard by proof index with no data-path collect
 collective of the path, an all-gather of the finished proofs (768 B each) over RCCL ("scaling": "weak").  Inputs
 (circuit polynomials, the MSM comb table of the SRS, witness columns) are resident in HBM before the timed region.
 
-OUTPUT.  stdout carries ONE JSON line of under 4 KB (asserted): the contract fields, `config` (workload + a dozen
-scalars), `roofline` (the dominant kernel, msm_comb_kernel, against the HBM roofline — durations from HIP events on the
-library's own streams, traffic from this round's committed PMC passes, the ALU view from this round's tools/ubench run
-and SQ counter passes — with `secondary` = the standalone 2^20 transform north_star puts a number on) and `cpu_baseline`
-(the oracle on one host core; the GPU proof of the same witness compared byte for byte).  EVERYTHING ELSE the run
-measures — BASELINE configs[2] (Poseidon) and configs[3] (2^16 .. 2^24 in both fields), the fallbacks (smaller tables,
-the bucket method, ec_lincomb on arbitrary bases), fresh uploads inside the timed region, single-proof latencies, host
-costs, clocks, per-rank figures, notes — goes to `bench_detail.json` (`--detail PATH`) and, as one line, to stderr.
-The legs live in tools/bench_legs.py.
+OUTPUT.  stdout carries ONE JSON line of under 4 KB (asserted): the contract fields and `config` (workload + a dozen
+scalars).  A plain run does only what that line needs: set-up, `--warmup` steps, the `--steps` timed steps, the outputs
+of the last timed step if `--dump-outputs DIR` is given, the line.  `ms_per_step` is the wall time of one timed step.
+
+`--dump-outputs DIR`: the proofs of the last timed step as its caller receives them (768 bytes each, global proof order)
+-> DIR/proofs.npy (float32 [P, 768], one byte per value) and DIR/proof_index.npy (float64 [P], the global index of each
+row); above DUMP_MAX_PROOFS proofs a fixed seeded sample.  The witnesses depend on the proof index only, so two builds
+run with the same arguments can be compared output for output.
+
+`--full` adds everything else the benchmark measures or checks, after the timed region: in the line `roofline` (the
+dominant kernel, msm_comb_kernel, against the HBM roofline — durations from HIP events on the library's own streams,
+recorded in the timed region, traffic from this round's committed PMC passes, the ALU view from this round's
+tools/ubench run and SQ counter passes — with `secondary` = the standalone 2^20 transform north_star puts a number on)
+and `cpu_baseline` (the oracle on one host core; the GPU proof of the same witness compared byte for byte); a few
+proofs of the last step under the pairing check (`sampled_proofs_verify`); and — in `bench_detail.json` (`--detail
+PATH`) and, as one line, on stderr — BASELINE configs[2] (Poseidon) and configs[3] (2^16 .. 2^24 in both fields), the
+fallbacks (smaller tables, the bucket method, ec_lincomb on arbitrary bases), fresh uploads inside the timed region,
+single-proof latencies, host costs, clocks, per-rank figures, notes.  The legs live in tools/bench_legs.py; the
+`--no-*` options and `--verify-samples` leave some of them out.
 """
 import argparse
 import json
@@ -55,6 +65,7 @@ def table_adds(info, n):
 # (1/16 of the device's memory) the one of 17 teeth (8.6 GB, 15)
 DEFAULT_TABLE_GB = 180.0
 LINE_LIMIT = 4096         # bytes of the stdout line (the driver's record keeps the last 8 KB of stdout)
+DUMP_MAX_PROOFS = 16384   # --dump-outputs: 16384 x 768 float32 values = 50 MB, under the 64 MB an output dump may take
 
 
 def chain_program_lines(n):
@@ -256,7 +267,7 @@ def _round(x, digits=6):
 
 
 def emit(line, detail, detail_path):
-    """ONE line on stdout, under LINE_LIMIT bytes; the detail beside it and on stderr."""
+    """ONE line on stdout, under LINE_LIMIT bytes; the detail (--full; None in a plain run) beside it and on stderr."""
     line = _round(line)
     text = json.dumps(line, separators=(",", ":"))
     for optional in (("per_rank", "proofs_per_s"), ("roofline", "secondary", "valu"), ("roofline", "valu"), ("roofline", "step_valu_source"), ("roofline", "valu_source"),
@@ -269,15 +280,31 @@ def emit(line, detail, detail_path):
         d.pop(optional[-1], None)
         text = json.dumps(line, separators=(",", ":"))
     assert len(text) < LINE_LIMIT, "bench line is %d bytes" % len(text)
-    detail = dict(detail, line=line)
-    try:
-        with open(detail_path, "w") as f:
-            json.dump(detail, f, indent=1)
-    except OSError as exc:
-        sys.stderr.write("bench.py: could not write %s: %r\n" % (detail_path, exc))
-    sys.stderr.write("bench_detail: " + json.dumps(detail) + "\n")
-    sys.stderr.flush()
+    if detail is not None:
+        detail = dict(detail, line=line)
+        try:
+            with open(detail_path, "w") as f:
+                json.dump(detail, f, indent=1)
+        except OSError as exc:
+            sys.stderr.write("bench.py: could not write %s: %r\n" % (detail_path, exc))
+        sys.stderr.write("bench_detail: " + json.dumps(detail) + "\n")
+        sys.stderr.flush()
     print(text, flush=True)
+
+
+def dump_outputs(outdir, gathered, total):
+    """`--dump-outputs DIR`: the last timed step's proofs, bytes as the gather hands them to the caller, one row per proof in
+    global order (a fixed seeded sample of DUMP_MAX_PROOFS rows when there are more)."""
+    import numpy as np
+
+    if total > DUMP_MAX_PROOFS:
+        idx = np.sort(np.random.default_rng(0).choice(total, DUMP_MAX_PROOFS, replace=False))
+    else:
+        idx = np.arange(total)
+    raw = np.frombuffer(b"".join(gathered[int(i)] for i in idx), dtype=np.uint8).reshape(len(idx), 768)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "proofs.npy"), raw.astype(np.float32))
+    np.save(os.path.join(outdir, "proof_index.npy"), idx.astype(np.float64))
 
 
 def preflight(args, ctx, comm, rank, world, local_rank, setup, comm_init_s, step_s, gather_ms, device_gather):
@@ -366,7 +393,14 @@ def main():
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs[2] (Poseidon)")
     ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's proofs to DIR/proofs.npy and DIR/proof_index.npy (see OUTPUT above)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline (roofline, CPU baseline, "
+                         "sampled verification, the legs of tools/bench_legs.py) and write the detail record; off by default")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # RCCL between processes needs dmabuf IPC on this driver (hipIpcGetMemHandle fails otherwise); the GPU boxes export this
     # already — set before the HIP runtime is loaded in case a launcher scrubbed the environment
@@ -494,12 +528,13 @@ def main():
         t_gen += t1 - t0
         t_pack += t2 - t1
         t_up += t3 - t2
-        if k == 0:
+        if k == 0 and args.full:
             t4 = time.perf_counter()
             pr.upload(wits)  # dicts -> bytes -> HBM in one call
             host_upload_ms = 1e3 * (time.perf_counter() - t4) / len(part)
     host_upload_packed_ms = 1e3 * t_up / per_gpu
-    t_up = host_upload_ms * 1e-3 * per_gpu  # what staging every batch from dictionaries would cost (the `host` block's end-to-end figure)
+    if args.full:
+        t_up = host_upload_ms * 1e-3 * per_gpu  # what staging every batch from dictionaries would cost (the `host` block's end-to-end figure)
 
     device_gather = comm is not None and comm.kind == "rccl" and not args.host_gather
     gather_ms = [0.0, 0.0, 0]  # this rank: collective ms, copy-to-host ms, gathers (reset before the timed region)
@@ -510,7 +545,7 @@ def main():
         for pr in provers:
             pr.run()                   # five rounds + transcript: one stream of kernel launches each
         if fault is not None and fault[0] == timed_step[0]:  # --inject-fault (tests): this rank dies or stalls mid-step
-            phase("INJECTED FAULT '%s' in timed step %d" % (fault[1], timed_step[0]))
+            phase("INJECTED FAULT '%s' in timed step %d at %.3f s since the epoch" % (fault[1], timed_step[0], time.time()))
             if fault[1] == "kill":
                 import signal
 
@@ -559,14 +594,15 @@ def main():
         if wd:
             wd.arm("preflight report", guard)
         return preflight(args, ctx, comm, rank, world, local_rank, setup, comm_init_s, step_s, gather_ms, device_gather)
-    for c in ctxs:
-        c.profile_reset()
-        c.profile(True)
+    if args.full:  # HIP events around every kernel of the timed region: the roofline's durations
+        for c in ctxs:
+            c.profile_reset()
+            c.profile(True)
     if wd:
         wd.arm("barrier before the timed region", guard)
     barrier()
     phase("warm-up done; timed region: %d steps" % args.steps)
-    sampler = ClockSampler(local_rank) if rank == 0 else None  # one sampler per job: rank 0's GPU
+    sampler = ClockSampler(local_rank) if rank == 0 and args.full else None  # one sampler per job: rank 0's GPU
     if sampler:
         sampler.start()
     gather_ms[:] = [0.0, 0.0, 0]
@@ -588,8 +624,9 @@ def main():
         wd.disarm()
     phase("timed region done: %.3f s" % elapsed)
     clocks = sampler.summary() if sampler else None
-    for c in ctxs:
-        c.profile(False)
+    if args.full:
+        for c in ctxs:
+            c.profile(False)
 
     def profile_sum(kernel):  # over every stream of this GPU
         ps = [c.profile_read(kernel) for c in ctxs]
@@ -602,37 +639,17 @@ def main():
     if args.dump_proofs and rank == 0:
         with open(args.dump_proofs, "wb") as f:
             f.write(b"".join(gathered[i] for i in range(total)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered, total)
 
     # the dominant kernel: the lookup MSM when the table fits in HBM (default), else the bucket method's accumulate
     info = setup.device_bases(ctx).lookup_info()
     lookup_bits = info["bits"]
     msm_kernel = {"comb": "msm_comb", "windows": "msm_lookup"}.get(info["layout"], "msm_accumulate")
-    msm_ms, msm_launches, msm_bytes = profile_sum(msm_kernel)
-    # The same kernel with the chip to itself: with several streams a launch's event-to-event duration includes the time
-    # it shares the CUs with the other streams' kernels, so the per-launch figures of the timed region understate the
-    # kernel.  A short untimed phase runs the batches of stream 0 alone (the other streams idle) and reads its events.
     knobs.close()  # the timed region's one-workgroup-per-MSM setting is for many streams: everything below runs one
-    iso = None
-    if NS > 1 and msm_launches:
-        barrier()
-        ctx.profile_reset()
-        ctx.profile(True)
-        for _ in range(max(3, -(-12 // len(provers[0::NS])))):  # (at least 48 launches of the kernel, however few batches stream 0 holds)
-            for pr in provers[0::NS]:
-                pr.run()
-                pr.download_raw()
-        ctx.sync()
-        ctx.profile(False)
-        i_ms, i_n, i_bytes = ctx.profile_read(msm_kernel)
-        if i_n:
-            iso = (i_ms * 1e-3 / i_n, i_bytes / i_n, i_n)
-        barrier()
     total_proofs = args.steps * total
     value = total_proofs / elapsed
     hbm_total = ctx.mem_info()[1]
-    run = legs.Run(ctx=ctx, ctxs=ctxs, comm=comm, world=world, rank=rank, local_rank=local_rank, setup=setup, program=program, provers=provers,
-                   parts=parts, blobs=blobs, mine=mine, B=B, S=S, NS=NS, per_gpu=per_gpu, steps=args.steps, value=value, barrier=barrier,
-                   group_order=GROUP_ORDER, witness_for=witness_for)
 
     config = {
         "workload": "configs[1]: group_order=2^%d, powersOfTau28_hez_final_11 SRS slice, synthetic squaring-chain witness, one distinct witness per proof" % args.log_n,
@@ -684,16 +701,6 @@ def main():
             "lagrange_commits": bool(args.lagrange_commits),
             "torch_imported": "torch" in sys.modules,  # the product and this file import no PyTorch: RCCL is reached through the C-ABI
         }),
-        "host": {
-            "host_upload_ms_per_proof": host_upload_ms,
-            "host_upload_prepacked_ms_per_proof": host_upload_packed_ms,
-            "witness_generation_ms_per_proof": 1e3 * t_gen / per_gpu,
-            "witness_packing_ms_per_proof": 1e3 * t_pack / per_gpu,
-            "end_to_end_proofs_per_s_from_dicts_per_gpu": per_gpu / (t_up + per_gpu * elapsed / total_proofs * world),
-            "note": "host_upload: BatchProver.upload, Python witness dictionaries -> 32-byte words (V x 32 B per proof) -> HBM, wire "
-                    "columns gathered on the device (timed on the first batch); prepacked: upload_values of already packed bytes "
-                    "(all batches); both synchronous and outside `value` (inputs are resident before the timed region)",
-        },
         "clocks": clocks,  # rank 0's GPU; None when rocm-smi prints nothing usable
     }
     if comm is not None:
@@ -721,6 +728,47 @@ def main():
         if comm.kind == "rccl":
             ri = comm.info()
             detail["config"].update({"rccl_path": ri["path"], "rccl_version": ri["version"], "rccl_calls_issued": ri["collectives"]})
+
+    if not args.full:  # a plain run: the headline line and nothing else
+        if rank == 0:
+            emit(line, None, None)
+        if comm is not None:
+            comm.barrier()
+            comm.close()
+        return
+
+    detail["host"] = {
+        "host_upload_ms_per_proof": host_upload_ms,
+        "host_upload_prepacked_ms_per_proof": host_upload_packed_ms,
+        "witness_generation_ms_per_proof": 1e3 * t_gen / per_gpu,
+        "witness_packing_ms_per_proof": 1e3 * t_pack / per_gpu,
+        "end_to_end_proofs_per_s_from_dicts_per_gpu": per_gpu / (t_up + per_gpu * elapsed / total_proofs * world),
+        "note": "host_upload: BatchProver.upload, Python witness dictionaries -> 32-byte words (V x 32 B per proof) -> HBM, wire "
+                "columns gathered on the device (timed on the first batch); prepacked: upload_values of already packed bytes "
+                "(all batches); both synchronous and outside `value` (inputs are resident before the timed region)",
+    }
+    msm_ms, msm_launches, msm_bytes = profile_sum(msm_kernel)
+    # The same kernel with the chip to itself: with several streams a launch's event-to-event duration includes the time
+    # it shares the CUs with the other streams' kernels, so the per-launch figures of the timed region understate the
+    # kernel.  A short untimed phase runs the batches of stream 0 alone (the other streams idle) and reads its events.
+    iso = None
+    if NS > 1 and msm_launches:
+        barrier()
+        ctx.profile_reset()
+        ctx.profile(True)
+        for _ in range(max(3, -(-12 // len(provers[0::NS])))):  # (at least 48 launches of the kernel, however few batches stream 0 holds)
+            for pr in provers[0::NS]:
+                pr.run()
+                pr.download_raw()
+        ctx.sync()
+        ctx.profile(False)
+        i_ms, i_n, i_bytes = ctx.profile_read(msm_kernel)
+        if i_n:
+            iso = (i_ms * 1e-3 / i_n, i_bytes / i_n, i_n)
+        barrier()
+    run = legs.Run(ctx=ctx, ctxs=ctxs, comm=comm, world=world, rank=rank, local_rank=local_rank, setup=setup, program=program, provers=provers,
+                   parts=parts, blobs=blobs, mine=mine, B=B, S=S, NS=NS, per_gpu=per_gpu, steps=args.steps, value=value, barrier=barrier,
+                   group_order=GROUP_ORDER, witness_for=witness_for)
 
     # HBM bytes per launch / per transform from the committed PMC passes of this round's build (rocprofv3 cannot run
     # inside this process): profiles/rNN_pmc_summary.json, written by tools/pmc_summary.py from tools/pmc_collect.sh;

@@ -8,11 +8,14 @@ import sys
 from conftest import EMU_LIB, REPO
 
 
-def _run(extra, timeout=600, detail=None):
+def _run(extra, timeout=600, detail=None, full=True):
     env = dict(os.environ, PLONK_HIP_LIB=EMU_LIB, PLONK_MSM_TABLE_GB="0.0001")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--log-n", "4", "--batch", "3", "--batches-per-step", "2", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-microbench", "--no-fallbacks", "--no-lookup", "--no-latency"] + extra
+           "--warmup", "1", "--no-lookup"]
+    if full:
+        cmd += ["--full", "--no-cpu-baseline", "--no-microbench", "--no-fallbacks", "--no-latency"]
+    cmd += extra
     if detail is not None:
         cmd += ["--detail", str(detail)]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -52,6 +55,41 @@ def test_gpus_flag_spawns_that_many_ranks(emu_cdll, tmp_path):
     assert len(line["per_rank"]["proofs_per_s"]) == 2  # the short form travels in the line
     # the detail also went to stderr as one line
     assert any(l.startswith("bench_detail: {") for l in r.stderr.splitlines())
+
+
+def test_a_plain_run_prints_the_line_and_dumps_the_last_steps_proofs(emu_cdll, tmp_path):
+    """Without --full: the contract line and nothing else (no detail record, roofline, CPU baseline or verification), the
+    number of timed steps as asked; --dump-outputs writes the last timed step's proofs, the bytes --dump-proofs writes."""
+    import numpy as np
+
+    out = tmp_path / "out"
+    r = _run(["--steps", "3", "--dump-proofs", str(tmp_path / "p.bin"), "--dump-outputs", str(out)], detail=tmp_path / "d.json", full=False)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _one_short_line(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0
+    assert abs(3 * line["ms_per_step"] - 1e3 * line["config"]["timed_region_s"]) <= 1e-4 * 3 * line["ms_per_step"]
+    assert "roofline" not in line and "cpu_baseline" not in line and "sampled_proofs_verify" not in line["config"]
+    assert not (tmp_path / "d.json").exists() and "bench_detail" not in r.stderr
+    proofs, idx = np.load(out / "proofs.npy"), np.load(out / "proof_index.npy")
+    assert proofs.dtype == np.float32 and proofs.shape == (6, 768) and idx.dtype == np.float64 and idx.tolist() == list(range(6))
+    assert proofs.astype(np.uint8).tobytes() == (tmp_path / "p.bin").read_bytes()
+
+
+def test_dump_outputs_samples_a_large_step_the_same_way_every_time(tmp_path, monkeypatch):
+    sys.path.insert(0, REPO)
+    import numpy as np
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_PROOFS", 4)
+    proofs = [bytes([i]) * 768 for i in range(10)]
+    bench.dump_outputs(str(tmp_path / "a"), proofs, 10)
+    bench.dump_outputs(str(tmp_path / "b"), proofs, 10)
+    idx = np.load(tmp_path / "a" / "proof_index.npy")
+    assert len(idx) == 4 and len(set(idx.tolist())) == 4 and list(idx) == sorted(idx) and 0 <= idx.min() and idx.max() < 10
+    assert (idx == np.load(tmp_path / "b" / "proof_index.npy")).all()
+    rows = np.load(tmp_path / "a" / "proofs.npy")
+    assert rows.shape == (4, 768) and all((rows[k] == idx[k]).all() for k in range(4))
 
 
 def test_force_comm_runs_the_multi_gpu_code_path_with_one_rank(emu_cdll, tmp_path):
@@ -130,35 +168,41 @@ GPU[1]		: Current Socket Graphics Package Power (W): 234.0
     assert bench.ClockSampler(0).summary() is None  # nothing sampled (no rocm-smi): the bench line carries null
 
 
+def _seconds_since_fault(stderr, mode):
+    """Wall time from the injected fault (the failing rank stamps it on its stderr, which the launcher repeats) to now: how long
+    the job took to notice and stop, whatever the start-up and the emulated steps before the fault cost on the host."""
+    import re
+    import time
+
+    m = re.search(r"INJECTED FAULT '%s' in timed step 1 at ([0-9.]+) s since the epoch" % mode, stderr)
+    assert m, stderr[-3000:]
+    return time.time() - float(m.group(1))
+
+
 def test_a_rank_that_dies_mid_step_stops_the_job_and_is_named(emu_cdll):
     """rank 1 exits between enqueueing its batches and the gather of timed step 1.  The launcher watches every rank:
     the job ends non-zero within seconds (not in a 30-minute timeout), names rank 1, its exit code and the tail of its stderr, and
     does not blame rank 0, which only lost its peer (PeerLost -> exit code 76)."""
-    import time
-
-    t0 = time.monotonic()
-    r = _run(["--gpus", "2", "--dist-backend", "sockets", "--no-end-to-end", "--steps", "3", "--inject-fault", "1:1:exit"], timeout=120)
-    took = time.monotonic() - t0
+    r = _run(["--gpus", "2", "--dist-backend", "sockets", "--no-end-to-end", "--steps", "3", "--inject-fault", "1:1:exit"])
     assert r.returncode != 0 and not r.stdout.strip(), (r.returncode, r.stdout[-500:])
     assert "rank 1 of 2 exited with code 17 first" in r.stderr, r.stderr[-3000:]
     assert "rank 0 exited with code 76 (it lost a peer)" in r.stderr and "PeerLost: rank 1 closed its connection" in r.stderr
     assert "INJECTED FAULT 'exit' in timed step 1" in r.stderr  # the stderr tail of the rank that failed
-    assert took < 60, took  # (start-up and one emulated warm-up step: ~15 s here; the failure itself is seen at once)
+    took = _seconds_since_fault(r.stderr, "exit")
+    assert took < 30, took  # (the failure itself is seen at once: the launcher's 2 s grace, process exits)
 
 
 def test_a_rank_that_hangs_mid_step_is_timed_out_and_named(emu_cdll):
     """The same with a rank that stops without exiting: the other rank's collective has a deadline (--comm-timeout), it gives up
-    naming the silent rank, and the launcher stops the stuck one."""
-    import time
-
-    t0 = time.monotonic()
-    r = _run(["--gpus", "2", "--dist-backend", "sockets", "--no-end-to-end", "--steps", "3", "--inject-fault", "1:1:hang", "--comm-timeout", "3"], timeout=120)
-    took = time.monotonic() - t0
+    naming the silent rank, and the launcher stops the stuck one.  The deadline is longer than two ranks of an emulated step drift
+    apart on a loaded host (a shorter one fires in the warm-up, before anything hangs)."""
+    r = _run(["--gpus", "2", "--dist-backend", "sockets", "--no-end-to-end", "--steps", "3", "--inject-fault", "1:1:hang", "--comm-timeout", "20"])
     assert r.returncode != 0 and not r.stdout.strip()
-    assert "PeerLost: rank 1 sent nothing for 3 s" in r.stderr, r.stderr[-3000:]
-    assert "rank 1 of 2 did not exit and had to be stopped (stuck?)" in r.stderr
+    assert "PeerLost: rank 1 sent nothing for 20 s" in r.stderr, r.stderr[-3000:]
+    assert "rank 1 of 2 did not exit and had to be stopped (stuck?)" in r.stderr, r.stderr[-3000:]
     assert "rank 1 stopped by the launcher while still running" in r.stderr
-    assert took < 60, took
+    took = _seconds_since_fault(r.stderr, "hang")
+    assert took < 20 + 30, took  # (the deadline, then the launcher's 2 s grace and the stop)
 
 
 def test_preflight_reports_every_rank(emu_cdll):

@@ -19,7 +19,7 @@ def test_eight_processes_share_the_gpu_and_gather_512_proofs(tmp_path):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--dist-backend", "sockets", "--steps", "1", "--warmup", "0",
-           "--batch", "64", "--batches-per-step", "1", "--streams", "1", "--lookup-budget-gb", "4", "--no-cpu-baseline",
+           "--batch", "64", "--batches-per-step", "1", "--streams", "1", "--lookup-budget-gb", "4", "--full", "--no-cpu-baseline",
            "--no-microbench", "--no-fallbacks", "--no-end-to-end", "--no-configs", "--no-latency", "--dump-proofs", str(dump),
            "--detail", str(tmp_path / "detail.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -56,7 +56,7 @@ def _bench(extra, timeout=1500, env_extra=None):
     env.update(env_extra or {})
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "detail.json")
-        cmd = [sys.executable, os.path.join(REPO, "bench.py")] + extra + ["--detail", path]
+        cmd = [sys.executable, os.path.join(REPO, "bench.py")] + extra + ["--full", "--detail", path]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
         assert r.returncode == 0, r.stderr[-3000:]
         detail = json.load(open(path))

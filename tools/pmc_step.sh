@@ -14,7 +14,7 @@ timeout 900 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_
     -d "$root/$out/step_issue" -o p -- python "$root/bench.py" --steps 1 --warmup 1 $SIDE --detail /tmp/step_detail_pmc.json "$@" \
     > "$root/$out/step_issue.json" 2> "$root/$out/step_issue.err"
 echo "step_issue rc=$?"
-timeout 600 python "$root/bench.py" --steps 10 --warmup 2 $SIDE --detail "$root/$out/step_plain_detail.json" "$@" \
+timeout 600 python "$root/bench.py" --steps 10 --warmup 2 --full $SIDE --detail "$root/$out/step_plain_detail.json" "$@" \
     > "$root/$out/step_plain.json" 2> "$root/$out/step_plain.err"
 echo "step_plain rc=$?"
 cd "$root"
