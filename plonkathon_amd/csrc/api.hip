@@ -572,7 +572,7 @@ static int srs_alloc(plonk_ctx* ctx, size_t n_points, plonk_srs** out) {
 }
 
 // Registry key of a base set: FNV-1a of the loaded bytes (a 64-bit hash is NOT an identity: the lookup-table registry compares
-// the bases themselves before it shares a table, msm.hip: lut_verified).
+// the bases themselves before it shares a table, msm_tables.h: lut_verified).
 // TEST HOOK, unsupported: with PLONK_ENABLE_TEST_HOOKS=1, PLONK_TEST_SRS_KEY replaces the hash by a constant so that the tests can
 // file two different base sets under ONE key and watch the registry tell them apart.  The salt (which keeps .ptau and affine
 // loads in separate key spaces) stays in force, and without the first variable the second is ignored: a stray setting in a
@@ -664,8 +664,10 @@ int plonk_msm_configure(plonk_ctx* ctx, unsigned window_bits, unsigned groups) {
 
 int plonk_srs_lookup_bits(const plonk_srs* srs, unsigned* out_bits) {
     PLONK_REQUIRE(srs && out_bits, PLONK_ERR_ARG, "bad argument");
-    *out_bits = srs->lookup_bits;
-    return PLONK_OK;
+    size_t bytes;
+    double build_s;
+    int sharers;
+    return msm_lookup_info(srs, out_bits, &bytes, &build_s, &sharers);
 }
 
 int plonk_srs_lookup_info(const plonk_srs* srs, unsigned* out_bits, size_t* out_bytes, double* out_build_s, int* out_sharers) {

@@ -186,7 +186,7 @@ PLONK_HD G1XyzzL g1l_from_xyzz(const G1Xyzz& p) {
 
 // acc += (x2, y2), canonical Montgomery coordinates.  Returns false WITHOUT touching acc when the step is
 // exceptional — identity base (0, 0), or P == +-Q (detected by a cheap filter with a 2^-25 false-positive
-// rate) — and the caller resolves it with the general packed formulas (msm.hip defers it to the bucket
+// rate) — and the caller resolves it with the general packed formulas (msm_bucket.h defers it to the bucket
 // reduction).  No calls, no packed arithmetic: minimal live registers.  neg_y adds (x2, -y2) instead: on signed limbs
 // the negation is 18 bit operations on y2, against ~40 instructions for a packed m - y and its select.
 //

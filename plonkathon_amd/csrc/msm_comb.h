@@ -1,6 +1,6 @@
-// msm_comb.h — fixed-base MSM on COMB tables (round 5).  Included by msm.hip after its common definitions.
+// msm_comb.h — fixed-base MSM on COMB tables (round 5).
 //
-// Same job as the window tables of msm.hip (ec_lincomb over a reusable SRS, /root/reference/curve.py:38-111 and
+// Same job as the window tables of msm_windows.h (ec_lincomb over a reusable SRS, /root/reference/curve.py:38-111 and
 // setup.py:66-72), fewer additions per base for the same memory.  With h teeth spaced a = ceil(254 / h) bits apart,
 // a scalar s is cut into a columns of h bits:  s = sum_{j < a} 2^j  sum_{k < h} b_(j + a k) 2^(a k),  and
 //     s P = sum_j 2^j  E_P[ bits j, j + a, j + 2a, .. ]      with ONE table per base,  E_P[idx] = sum_k (+-) 2^(a k) P.
@@ -27,7 +27,7 @@
 //                               TOP: a workgroup takes whole groups of g scalars and adds the digits of the virtual scalars
 //   msm_comb_kernel             one workgroup per (MSM, scalar sub-range).  Lanes are bound to COLUMNS (a lane's accumulator can
 //                               only hold one column's sum): q = 256 / a lanes per column walk scalars r, r + q, .. — the whole
-//                               chip reads the tables of q consecutive bases at a time (address translation: msm.hip,
+//                               chip reads the tables of q consecutive bases at a time (address translation: msm_windows.h,
 //                               msm_lookup_kernel) — for p = ceil(a n / 256) steps, and the 256 - a q lanes left over take the
 //                               scalars the columns' lanes did not reach, column after column, leaving one partial sum
 //                               ("piece") in LDS per column they touch.  Every lane performs p additions (+-0): 104 for 2^11
@@ -42,6 +42,9 @@
 // Gray-code order (one mixed addition of +-2 G_k per entry); g1_batch_to_affine_kernel converts a chunk of bases at a time;
 // msm_comb_top_base_kernel / msm_comb_top_fill_kernel: the joint tables, one block of 2^(h-1) entries per group behind the bases' blocks.
 #pragma once
+#include <utility>
+
+#include "msm_common.h"
 
 #define MSM_COMB_MAX_TEETH 24
 #define MSM_COMB_SEG_BITS 8
@@ -245,7 +248,7 @@ __global__ void __launch_bounds__(64) msm_comb_top_fill_kernel(const G1Affine* t
 }
 
 // digits[(m * A + j) * nd + i] = column j of scalar i of MSM m: the index of its table entry in bits 0 .. H-2, bit 31 set when the
-// entry is to be subtracted.  Scalar vector of MSM m as in msm_sort_kernel (stride / inner / outer_stride).  nd = n without top
+// entry is to be subtracted.  Scalar vector of MSM m: msm_scalar_row.  nd = n without top
 // tables.  TOP (see msm_comb_shape): a workgroup takes PER = g floor(256 / g) scalars — whole groups — and, after the columns,
 // lane t < PER / g folds the top codes of its group into the digit of virtual scalar n + grp / A of column grp % A
 // (nd = n + ceil(ceil(n / g) / A); a group past the last scalar gets the all-zero code: the identity entry of its block).
@@ -259,7 +262,7 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
     const bool live = threadIdx.x < PER && i < n;
     int code = 0;
     if (live) {
-        const Fr* sc = scalars + (m % inner) * stride + (m / inner) * outer_stride;
+        const Fr* sc = msm_scalar_row(scalars, m, stride, inner, outer_stride);
         const Fr s = fp_load(sc + i);  // the Montgomery residue s R mod r, taken as the integer it is: the table holds multiples of R^-1 P
         // odd representative: s, or r - s with the sign of the base flipped (r is odd; s = 0 becomes r, and r P = O comes out of the sums)
         const bool even = !(s.v[0] & 1u);
@@ -490,12 +493,7 @@ template <unsigned LPM> __global__ void __launch_bounds__(64) msm_comb_finalize_
     if constexpr (LPM >= 32) ok &= g1l_wave_reduce_step<16, true>(acc, lane);
     if constexpr (LPM >= 64) ok &= g1l_wave_reduce_step<32, true>(acc, lane);
     if (m < M && !ok) atomicOr(n_deferred + m, MSM_COMB_REDO);
-    if (m < M && l == 0) {
-        G1Affine r = g1_to_affine(g1l_to_xyzz(acc));
-        flags[m] = g1_affine_is_identity(r) ? 1 : 0;
-        fp_store(out_xy + 2 * m, fp_from_mont(r.x));
-        fp_store(out_xy + 2 * m + 1, fp_from_mont(r.y));
-    }
+    if (m < M && l == 0) msm_store_result(g1l_to_xyzz(acc), m, out_xy, flags);
 }
 
 // Recovery path (MSM_DEFER_CAP): MSM m recomputed from its digits with the general formulas; one workgroup per MSM, which exits
@@ -521,28 +519,10 @@ __global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* look
             g1_madd<true>(acc, pt);
         }
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (unsigned s = 128; s >= 64; s >>= 1) {
-        if (tid < s) {
-            G1Xyzz x = red[tid];
-            g1_add(x, red[tid + s]);
-            red[tid] = x;
-        }
-        __syncthreads();
-    }
-    if (tid >= 64) return;
-    G1Xyzz total = red[tid];
-    g1_wave_reduce(total, tid);
-    if (tid == 0) {
-        G1Affine r = g1_to_affine(total);
-        flags[m] = g1_affine_is_identity(r) ? 1 : 0;
-        fp_store(out_xy + 2 * m, fp_from_mont(r.x));
-        fp_store(out_xy + 2 * m + 1, fp_from_mont(r.y));
-    }
+    msm_fold_store(red, acc, tid, 256, m, out_xy, flags);
 }
 
-// Verification of a comb table found in the registry by its 64-bit key (msm.hip, lut_verified), against THIS SRS's bases:
+// Verification of a comb table found in the registry by its 64-bit key (msm_tables.h, lut_verified), against THIS SRS's bases:
 //   every base: the all-ones entry = (sum_k 2^(a k)) R^-1 P_i, recomputed by doublings and additions from the base;
 //   LUT_VERIFY_SAMPLES bases: entry 0 (every lower tooth -1) and the entry of the alternating index 0101.. as well.
 // A table of another tooth count / spacing, or of other bases, filed under the same key fails here.
@@ -601,3 +581,215 @@ __global__ void __launch_bounds__(64) msm_comb_verify_top_kernel(const G1Affine*
     const bool ok = g1_is_identity(sum) ? (fp_is_zero(ex) && fp_is_zero(ey)) : (fp_eq(fp_mul(ex, sum.zz), sum.x) && fp_eq(fp_mul(ey, sum.zzz), sum.y));
     if (!ok) atomicAdd(mismatches, 1u);
 }
+
+// ---- host side ---------------------------------------------------------------------------------
+// XYZZ staging of the build: an eighth of the table's entries at a time (whole bases), at most 2^27 of them (17 GB)
+static size_t msm_comb_stage_entries(size_t n, unsigned h) {
+    const size_t half = (size_t)1 << (h - 1);
+    size_t bases = n / 8 ? n / 8 : 1;
+    while (bases > 1 && bases * half > ((size_t)1 << 27)) bases /= 2;
+    return bases * half;
+}
+static size_t msm_comb_bytes(size_t n, unsigned h, bool top) {  // table + staging
+    return (msm_comb_blocks(n, msm_comb_shape(h, top)) << (h - 1)) * sizeof(G1Affine) + msm_comb_stage_entries(n, h) * sizeof(G1Xyzz);
+}
+static double msm_comb_additions(unsigned h, bool top) {
+    const MsmCombShape sh = msm_comb_shape(h, top);
+    return (double)sh.a + (top ? 1.0 / sh.top_g : 0.0);
+}
+bool msm_comb_takes_top(unsigned teeth) { return teeth >= 2 && teeth <= MSM_COMB_MAX_TEETH && msm_comb_top_ok(teeth); }
+static bool msm_comb_takes_top_for(size_t n, unsigned h) { return msm_comb_top_ok(h) && msm_comb_top_reach_ok(n, msm_comb_shape(h, true)); }
+static bool msm_comb_well_formed(const MsmLookupTable* t) {
+    if (t->bits < 2 || t->bits > MSM_COMB_MAX_TEETH) return false;
+    const bool top = t->top_g != 0;
+    if (top && !msm_comb_top_ok(t->bits)) return false;
+    const MsmCombShape sh = msm_comb_shape(t->bits, top);
+    return t->windows == sh.a && t->top_bits == sh.top_bits && t->top_g == sh.top_g &&
+           t->bytes == (msm_comb_blocks(t->n_points, sh) << (t->bits - 1)) * sizeof(G1Affine);
+}
+
+// R^-1 mod r as a plain integer (R = 2^261, Fr's Montgomery radix): the comb tables hold multiples of R^-1 P_i
+static MsmCombScale msm_comb_scale_constant() {
+    Fr one_plain = fp_zero<FrParams>();
+    one_plain.v[0] = 1;
+    const Fr c = fp_from_mont(one_plain);  // fp_from_mont multiplies the integer it is given by R^-1 mod r: here the integer 1
+    MsmCombScale k;
+    for (int i = 0; i < 8; i++) k.c[i] = c.v[i];
+    return k;
+}
+
+// Builds the comb table of h teeth; top: with top tables (floor(254 / h) columns, a joint table per group of bases for the bits left over)
+static int msm_comb_build(plonk_ctx* ctx, const plonk_srs* srs, unsigned h, bool top, MsmLookupTable* t) {
+    if (top && !msm_comb_top_ok(h)) {
+        plonk_set_error("a comb of %u teeth takes no top tables (254 mod teeth must be 1 or 2)", h);
+        return PLONK_ERR_ARG;
+    }
+    const MsmCombShape sh = msm_comb_shape(h, top);
+    if (!msm_comb_top_reach_ok(srs->n_points, sh)) {
+        plonk_set_error("%zu bases are too many for the top tables of a %u-tooth comb (a virtual scalar's block offset must fit 31 bits)", srs->n_points, h);
+        return PLONK_ERR_ARG;
+    }
+    const unsigned a = sh.a, sb = h - 1 < MSM_COMB_SEG_BITS ? h - 1 : MSM_COMB_SEG_BITS;
+    const size_t n = srs->n_points, half = (size_t)1 << (h - 1), stage = msm_comb_stage_entries(n, h), chunk_bases = stage / half;
+    const size_t blocks = msm_comb_blocks(n, sh);
+    void *gx = nullptr, *gb = nullptr, *dx = nullptr, *db = nullptr, *tmp = nullptr, *tab = nullptr, *pb = nullptr;
+    auto fail = [&]() {
+        for (void* q : {gx, gb, dx, db, tmp, tab, pb})
+            if (q) hipFree(q);
+        (void)hipGetLastError();
+        plonk_set_error("the %u-tooth comb table (%zu MiB) does not fit in device memory", h, msm_comb_bytes(n, h, top) >> 20);
+        return PLONK_ERR_NOMEM;
+    };
+    if (!plonk_dev_malloc(&tab, blocks * half * sizeof(G1Affine))) return fail();
+    if (!plonk_dev_malloc(&tmp, stage * sizeof(G1Xyzz))) return fail();
+    if (!plonk_dev_malloc(&gx, n * h * sizeof(G1Xyzz))) return fail();
+    if (!plonk_dev_malloc(&gb, n * h * sizeof(G1Affine))) return fail();
+    if (!plonk_dev_malloc(&dx, n * (sb ? sb : 1) * sizeof(G1Xyzz))) return fail();
+    if (!plonk_dev_malloc(&db, n * (sb ? sb : 1) * sizeof(G1Affine))) return fail();
+    if (!plonk_dev_malloc(&pb, n * sizeof(G1Affine))) return fail();
+    // P'_i = R^-1 P_i (the scalars arrive as Montgomery residues), through the staging buffers of the next step
+    PLONK_LAUNCH(msm_comb_scale_kernel, grid1(n, 64, 2048), dim3(64), 0, ctx->stream, (const G1Affine*)srs->bases, n, msm_comb_scale_constant(), (G1Xyzz*)gx);
+    g1_batch_to_affine(ctx, (const G1Xyzz*)gx, (G1Affine*)pb, n);
+    // tooth points G_k = 2^(a k) P'_i (k < h) and the Gray-code steps 2 G_k (k < sb), affine
+    msm_window_bases(ctx, (const G1Affine*)pb, n, a, h, (G1Xyzz*)gx);
+    g1_batch_to_affine(ctx, (const G1Xyzz*)gx, (G1Affine*)gb, n * h);
+    if (sb) {
+        PLONK_LAUNCH(msm_comb_delta_kernel, grid1(n * sb), dim3(256), 0, ctx->stream, (const G1Affine*)gb, n * sb, (G1Xyzz*)dx);
+        g1_batch_to_affine(ctx, (const G1Xyzz*)dx, (G1Affine*)db, n * sb);
+    }
+    for (size_t i0 = 0; i0 < n; i0 += chunk_bases) {
+        const size_t nb = n - i0 < chunk_bases ? n - i0 : chunk_bases, lanes = nb << (h - 1 - sb);
+        PLONK_LAUNCH(msm_comb_fill_kernel, grid1(lanes, 64, 65536), dim3(64), 0, ctx->stream, (const G1Affine*)gb, (const G1Affine*)db, n, i0, nb, h, sb,
+                     (G1Xyzz*)tmp);
+        g1_batch_to_affine(ctx, (const G1Xyzz*)tmp, (G1Affine*)tab + i0 * half, nb * half);
+    }
+    if (top) {
+        // tooth points of the top tables 2^(L - j) P'_i (through gx / gb, free by now), then the joint tables a chunk of groups at a
+        // time; a block past the last group (the columns are padded to equal lengths) stays all identity
+        PLONK_LAUNCH(msm_comb_top_base_kernel, grid1(n, 64, 2048), dim3(64), 0, ctx->stream, (const G1Affine*)pb, n, a * h, a, sh.top_g, (G1Xyzz*)gx);
+        g1_batch_to_affine(ctx, (const G1Xyzz*)gx, (G1Affine*)gb, n);
+        const size_t groups = msm_comb_top_groups(n, sh.top_g), vblocks = blocks - n, run = sh.top_g >= 2 ? (size_t)sh.top_b * sh.top_b : sh.top_b;
+        for (size_t g0 = 0; g0 < vblocks; g0 += chunk_bases) {
+            const size_t nb = vblocks - g0 < chunk_bases ? vblocks - g0 : chunk_bases;
+            const size_t ng = g0 >= groups ? 0 : (groups - g0 < nb ? groups - g0 : nb);
+            if (hipMemsetAsync(tmp, 0, nb * half * sizeof(G1Xyzz), ctx->stream) != hipSuccess) return fail();
+            if (ng)
+                PLONK_LAUNCH(msm_comb_top_fill_kernel, grid1(ng * (sh.top_entries / run), 64, 65536), dim3(64), 0, ctx->stream, (const G1Affine*)gb, n, g0, ng,
+                             h - 1, sh.top_g, sh.top_b, sh.top_entries, (G1Xyzz*)tmp);
+            g1_batch_to_affine(ctx, (const G1Xyzz*)tmp, (G1Affine*)tab + (n + g0) * half, nb * half);
+        }
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return fail();
+    for (void* q : {gx, gb, dx, db, tmp, pb}) hipFree(q);
+    t->kind = MSM_TABLE_COMB;
+    t->bits = h;
+    t->windows = a;
+    t->top_bits = sh.top_bits;
+    t->top_g = sh.top_g;
+    t->data = (G1Affine*)tab;
+    t->bytes = blocks * half * sizeof(G1Affine);
+    return PLONK_OK;
+}
+
+static void msm_comb_verify(plonk_ctx* ctx, const plonk_srs* srs, const MsmLookupTable* t, unsigned* d_mismatches) {
+    const size_t lanes = srs->n_points + 2 * LUT_VERIFY_SAMPLES;
+    PLONK_LAUNCH(msm_comb_verify_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, ctx->stream, (const G1Affine*)srs->bases,
+                 (const G1Affine*)t->data, srs->n_points, t->windows, t->bits, (unsigned)LUT_VERIFY_SAMPLES, msm_comb_scale_constant(), d_mismatches);
+    if (t->top_g) {
+        const size_t groups = msm_comb_top_groups(srs->n_points, t->top_g);
+        PLONK_LAUNCH(msm_comb_verify_top_kernel, dim3((unsigned)((groups + 63) / 64)), dim3(64), 0, ctx->stream, (const G1Affine*)srs->bases,
+                     (const G1Affine*)t->data, srs->n_points, t->windows, t->bits, t->top_g, (2u << t->top_bits) - 1u, msm_comb_scale_constant(),
+                     d_mismatches);
+    }
+}
+
+// digits kernel of the comb with h teeth (one instantiation per tooth count: the bit gather is unrolled at compile time); TOP: the
+// comb with top tables, whose workgroups take whole groups of scalars and add the virtual scalars' digits (nd = n + their number)
+template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ctx, const Fr* d_scalars, size_t n, size_t stride, size_t inner,
+                                                                   size_t outer_stride, size_t M, uint32_t* digits, size_t nd) {
+    if constexpr (!TOP || msm_comb_top_ok(H)) {
+        constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
+        constexpr unsigned G = TOP ? SH.top_g : 1, PER = (256 / G) * G;
+        size_t gx = (n + PER - 1) / PER;
+        if (TOP) {  // every virtual scalar's digit is written, also those of the groups past the last scalar
+            const size_t gv = ((nd - n) * SH.a + PER / G - 1) / (PER / G);
+            gx = gx > gv ? gx : gv;
+        }
+        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
+        for (size_t m0 = 0; m0 < M; m0 += 32768) {  // (a grid's second dimension ends at 65 535)
+            const size_t rows = M - m0 < 32768 ? M - m0 : 32768;
+            PLONK_LAUNCH(kern, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, ctx->stream, d_scalars, n, stride, inner,
+                         outer_stride, m0, digits, nd);
+        }
+    }
+}
+typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t);
+template <bool TOP, unsigned... H> static msm_comb_digits_fn msm_comb_digits_for(unsigned h, std::integer_sequence<unsigned, H...>) {
+    msm_comb_digits_fn fn = nullptr;
+    ((h == H + 2 && (!TOP || msm_comb_top_ok(H + 2)) ? (void)(fn = &msm_comb_launch_digits<H + 2, TOP>) : (void)0), ...);
+    return fn;
+}
+
+static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalars, size_t n_real, size_t M, size_t stride, Fq* d_out_xy, uint8_t* d_flags,
+                        size_t inner, size_t outer_stride) {
+    const G1Affine* table = srs->shared->data;
+    const unsigned h = srs->shared->bits, a = srs->shared->windows, hb = h - 1;
+    // top tables: the kernels see n = n_real + nv scalars, the last nv of each column being its share of the groups
+    const bool top = srs->shared->top_g != 0;
+    const MsmCombShape sh = msm_comb_shape(h, top);
+    const size_t nv = msm_comb_virtual(n_real, sh), n = n_real + nv;
+    const unsigned top_delta = (unsigned)(srs->n_points - n_real);  // block of virtual scalar n_real + v = n_points + v (+ the digit's offset)
+    PLONK_REQUIRE((uint64_t)n * a < ((uint64_t)1 << 32), PLONK_ERR_ARG, "MSM size %zu too large for the lookup path", n_real);
+    PLONK_REQUIRE(msm_comb_top_reach_ok(n_real, sh), PLONK_ERR_ARG, "MSM size %zu too large for the top tables of %u teeth", n_real, h);
+    // enough waves to occupy 1024 SIMDs three to four deep, in as few workgroups per MSM as that takes; at least two additions per lane
+    unsigned G = msm_groups_per_msm(ctx, M, 64, 3072 / (MSM_BLOCK / 64), 0.035, n * a, 2);
+    while (G > 1 && (size_t)G > n) G /= 2;
+    MsmScratch s;
+    const size_t part_off = s.take(M * G * a * sizeof(G1Xyzz)), col_off = s.take(G >= 4 ? M * a * sizeof(G1Xyzz) : 0), cnt_off = s.take(M * 4);
+    const size_t dfr_off = s.take(M * MSM_DEFER_CAP * sizeof(MsmDeferred)), dig_off = s.take(M * a * n * 4);
+    PLONK_TRY(ctx_scratch(ctx, 1, s.total, (void**)&s.base));
+    G1Xyzz *partial = s.at<G1Xyzz>(part_off), *colsum = s.at<G1Xyzz>(col_off);
+    uint32_t *n_deferred = s.at<uint32_t>(cnt_off), *digits = s.at<uint32_t>(dig_off);
+    MsmDeferred* deferred = s.at<MsmDeferred>(dfr_off);
+    const auto teeth = std::make_integer_sequence<unsigned, MSM_COMB_MAX_TEETH - 1>();
+    const msm_comb_digits_fn digits_fn = top ? msm_comb_digits_for<true>(h, teeth) : msm_comb_digits_for<false>(h, teeth);
+    PLONK_REQUIRE(digits_fn, PLONK_ERR_ARG, "no comb of %u teeth", h);
+    PLONK_CHECK_HIP(hipMemsetAsync(n_deferred, 0, M * 4, ctx->stream));
+    PLONK_TRY(prof_begin(ctx, "msm_digits", (double)M * (double)n * (32.0 + 4.0 * a)));
+    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n);
+    PLONK_TRY(prof_end(ctx));
+    const size_t lds = (size_t)(MSM_BLOCK + a) * sizeof(G1Xyzz);
+    PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));
+    PLONK_LAUNCH(msm_comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a, (const uint32_t*)digits, n, G, partial,
+                 deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
+    PLONK_TRY(prof_end(ctx));
+    const G1Xyzz* sums = partial;
+    unsigned Gf = G;
+    if (G >= 4) {  // few MSMs in many pieces: a wave per (MSM, column) sums the pieces in parallel
+        PLONK_LAUNCH(msm_comb_colsum_kernel, dim3((unsigned)(M * a)), dim3(64), 0, ctx->stream, (const G1Xyzz*)partial, G, a, colsum, n_deferred);
+        sums = colsum;
+        Gf = 1;
+    }
+    // lanes per MSM in the Horner step (chain of a - 1 doublings and the additions between them, on lazy limbs): four for a batch
+    // (12 doublings + 6 additions per lane, 16 MSMs per wave), sixteen when the MSMs are few (12 + 4: the shortest chain);
+    // one lane per MSM would be the least work and the longest chain (12 + 12).
+#define PLONK_COMB_FINALIZE(L)                                                                                                                      \
+    PLONK_LAUNCH(msm_comb_finalize_kernel<L>, dim3((unsigned)((M * L + 63) / 64)), dim3(64), 0, ctx->stream, sums, M, Gf, a, table, hb, n,            \
+                 (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, n_deferred, d_out_xy, d_flags, (unsigned)n_real, top_delta)
+    if (M >= 64) PLONK_COMB_FINALIZE(4);
+    else PLONK_COMB_FINALIZE(16);
+#undef PLONK_COMB_FINALIZE
+    PLONK_LAUNCH(msm_comb_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, n, (const uint32_t*)n_deferred,
+                 d_out_xy, d_flags, (unsigned)n_real, top_delta);
+    PLONK_CHECK_HIP(hipGetLastError());
+    return PLONK_OK;
+}
+
+static const MsmTableLayout msm_comb_layout = {22,
+                                               msm_comb_takes_top_for,
+                                               msm_comb_additions,
+                                               msm_comb_bytes,
+                                               msm_comb_well_formed,
+                                               msm_comb_build,
+                                               msm_comb_verify,
+                                               msm_run_comb};

@@ -84,7 +84,7 @@ struct NttTables {
 #define MSM_TABLE_COMB 1
 #define MSM_TABLE_WINDOWS 2
 // One lookup table per (process, device, base set), shared by every plonk_srs / context / stream that
-// loads the same bases (msm.hip keeps the registry; reference counted, freed with its last plonk_srs).
+// loads the same bases (msm_tables.h keeps the registry; reference counted, freed with its last plonk_srs).
 struct MsmLookupTable {
     int device = 0;
     uint64_t key = 0;        // FNV-1a of the host bytes the bases were loaded from
@@ -92,7 +92,7 @@ struct MsmLookupTable {
     unsigned kind = 0;       // MSM_TABLE_COMB (msm_comb.h: bits = teeth h, windows = columns a) or MSM_TABLE_WINDOWS (bits = c, windows = W)
     unsigned bits = 0, windows = 0;
     unsigned top_bits = 0, top_g = 0;  // comb with top tables (msm_comb.h: windows = floor(254 / bits)): R and the bases per group; 0, 0 = none
-    G1Affine* data = nullptr;
+    G1Affine* data = nullptr;  // comb: data[(i << (h - 1)) + idx]; windows: data[((w * n_points + i) << (c - 1)) + d - 1]
     size_t bytes = 0;
     double build_s = 0;      // wall time of the build (reported by bench.py)
     int refs = 0;
@@ -106,15 +106,10 @@ struct plonk_srs {
     unsigned window_bits = 0;   // c of the current window table (0 = not built)
     unsigned n_windows = 0;
     G1Affine* table = nullptr;  // device: table[w * n_points + i] = 2^(c*w) * bases[i]
-    // lookup MSM (msm.hip): every multiple d * 2^(c*w) * bases[i], d = 1 .. 2^(c-1), resident in HBM
+    // table MSM (msm_tables.h): multiples of the bases resident in HBM
     bool fixed = false;          // a reusable SRS (plonk_srs_load_ptau): worth a big table
-    unsigned lookup_bits = 0;    // teeth h of the comb table / window bits c of the window table (0 = none)
-    unsigned lookup_windows = 0; // additions per base: columns a of the comb / windows W
-    unsigned lookup_kind = 0;    // MSM_TABLE_COMB / MSM_TABLE_WINDOWS (0 = none)
-    unsigned lookup_top_bits = 0, lookup_top_g = 0;  // the attached comb's top tables (0, 0 = none)
     bool lookup_failed = false;  // an automatic build did not fit: do not retry on every call
-    G1Affine* lookup = nullptr;  // comb: lookup[(i << (h - 1)) + idx]; windows: lookup[((w * n_points + i) << (c - 1)) + d - 1]   (= shared->data)
-    MsmLookupTable* shared = nullptr;
+    MsmLookupTable* shared = nullptr;  // the attached table (null = none)
     // Lagrange-basis SRS (setup.py:66-72 without the ifft): lagrange[log_n] = [L_i(tau)]_1, i < 2^log_n, built on
     // demand by an EC inverse NTT of the first 2^log_n bases (msm.hip); each is a plonk_srs of its own.
     std::map<unsigned, plonk_srs*> lagrange;
@@ -138,7 +133,7 @@ struct plonk_ctx {
     unsigned msm_lookup_bits = 0;    // 0 = the table with the fewest additions per base that fits the budget
     bool msm_lookup_top = false;     // with explicit msm_lookup_bits: the comb WITH top tables (plonk_msm_lookup_configure mode | 32)
     unsigned msm_lookup_kind = MSM_TABLE_COMB;  // layout of the tables this context builds (plonk_msm_lookup_configure: mode | 16 = window tables)
-    size_t msm_lookup_budget = 0;    // bytes; 0 = default (PLONK_MSM_TABLE_GB if set, else min(device memory / 16, free memory / 4): msm.hip)
+    size_t msm_lookup_budget = 0;    // bytes; 0 = default (PLONK_MSM_TABLE_GB if set, else min(device memory / 16, free memory / 4): msm_tables.h)
     bool ntt_attr_set = false, msm_attr_set = false;  // hipFuncSetAttribute is per device: tracked per context
     // per-kernel HIP-event profiling (bench.py roofline): one record per instrumented launch
     struct ProfRec { const char* name; hipEvent_t a, b; double algo_bytes; };
@@ -153,6 +148,14 @@ struct plonk_ctx {
     unsigned ntt_cfg_epoch = 0;  // bumped by every plonk_ntt_* setter: cached launch plans are rebuilt
     unsigned ntt_kind = 0;  // 0 = auto (wave kernels where they apply, else the LDS kernel), 1 / 4 = the LDS kernel, 5 = force wave, 6 / 7 = force wave without / with the two-element latency forms, 8 = force wave with 2^12 on 1024 threads
 };
+
+// grid of a grid-stride kernel over n items
+static inline dim3 grid1(size_t n, unsigned block = 256, size_t cap = 4096) {
+    size_t g = (n + block - 1) / block;
+    if (g > cap) g = cap;
+    if (!g) g = 1;
+    return dim3((unsigned)g);
+}
 
 // scratch slot use: 0 = NTT inter-pass buffer, 1 = MSM digits/partials, 2-3 = API-level temporaries
 int ctx_scratch(plonk_ctx* ctx, int slot, size_t bytes, void** out);
@@ -195,16 +198,17 @@ bool ntt_wave_plan(const plonk_ctx* ctx /* null: the default splits */, unsigned
 int ntt_dist_columns(plonk_ctx*, const Fr* in, Fr* out, unsigned log_n, unsigned log_w, unsigned rank, bool inverse);
 int ntt_dist_rows(plonk_ctx*, const Fr* in, Fr* out, unsigned log_n, unsigned log_w, unsigned rank, bool inverse);
 // msm.hip
-int msm_build_table(plonk_ctx*, plonk_srs*, unsigned c);
 int msm_lagrange_srs(plonk_ctx*, plonk_srs*, unsigned log_n, plonk_srs** out);  // owned by (and freed with) the parent
-void g1_batch_to_affine(plonk_ctx*, const G1Xyzz* in, G1Affine* out, size_t n);  // enqueue: XYZZ -> affine (Montgomery), identity -> (0, 0)
+void g1_batch_to_affine(plonk_ctx*, const G1Xyzz* in, G1Affine* out, size_t n, size_t max_groups = 65536);  // enqueue: XYZZ -> affine (Montgomery), identity -> (0, 0)
+void msm_window_bases(plonk_ctx*, const G1Affine* bases, size_t n, unsigned c, unsigned W, G1Xyzz* out);  // enqueue: out[w * n + i] = 2^(c w) bases[i]
 // g1_ntt.hip: the same Lagrange-basis points by an inverse DFT over the group (n log n group operations)
 int g1_lagrange_by_ntt(plonk_ctx*, const plonk_srs*, unsigned log_n, G1Affine* d_bases_out);
+// msm_tables.h
 void msm_srs_release(plonk_srs*);  // drops the reference on the shared lookup table
 int msm_lookup_info(const plonk_srs*, unsigned* bits, size_t* bytes, double* build_s, int* sharers);
 int msm_lookup_layout(const plonk_srs*, unsigned* kind, unsigned* additions_per_base);
 int msm_lookup_top(const plonk_srs*, unsigned* top_bits, unsigned* bases_per_group);
-bool msm_comb_takes_top(unsigned teeth);  // msm.hip: a comb of this many teeth can take top tables
+bool msm_comb_takes_top(unsigned teeth);  // msm_comb.h: a comb of this many teeth can take top tables
 uint64_t plonk_fnv1a64(const void* data, size_t n);
 // MSM m reads its scalars at d_scalars + (m % inner) * stride + (m / inner) * outer_stride (inner = 0: inner = M)
 int msm_run_device(plonk_ctx*, plonk_srs*, const Fr* d_scalars, size_t n, size_t M, size_t stride, Fq* d_out_xy,

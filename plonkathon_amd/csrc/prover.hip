@@ -89,13 +89,6 @@ struct plonk_prover {
     ChallengeConsts chal;   // 2^(256 j) R^2 mod r, for the challenge reduction in transcript_kernel
 };
 
-static inline dim3 grid1(size_t n, unsigned block = 256, size_t cap = 4096) {
-    size_t g = (n + block - 1) / block;
-    if (g > cap) g = cap;
-    if (!g) g = 1;
-    return dim3((unsigned)g);
-}
-
 // ------------------------------------------------------------------------------------------------
 // witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
 __global__ void pi_fill_kernel(const Fr* pub, size_t n_public, size_t n, size_t B, Fr* pi) {

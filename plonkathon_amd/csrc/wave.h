@@ -9,7 +9,7 @@
 //   g1_wave_suffix_scan(p, lane)  lane l <- p_l + .. + p_63 (the weighting of the bucket reduction)
 //   g1_wave_reduce(p, lane)       butterfly sum of one G1 point per lane: afterwards every lane holds the total
 //                                 ("wave-reduced bucket sum": the last six levels of the MSM reductions)
-// Used by the NTT wave kernels (ntt.hip) for their in-register digit exchanges and by the MSM kernels (msm.hip).
+// Used by the NTT wave kernels (ntt.hip) for their in-register digit exchanges and by the MSM kernels (msm_common.h, msm_bucket.h, msm_windows.h, msm_comb.h).
 #pragma once
 #include "g1.h"
 

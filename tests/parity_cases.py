@@ -654,7 +654,7 @@ def lincomb_golden(setup, full_size=True):
         assert affine(got) == pt(case["result"]), case["name"]
     assert pa.ec_lincomb([(None, 5), (Pts[2], 1)]) == Pts[2]
     # duplicate bases: every addition inside a bucket hits P == +-Q, the case the MSM's fast formulas defer to
-    # the bucket reduction (csrc/msm.hip); 40 x the same point with the same scalar, then with cancelling signs
+    # the bucket reduction (csrc/msm_bucket.h); 40 x the same point with the same scalar, then with cancelling signs
     g2, s7 = affine(Pts[2]), 0x1234567890ABCDEF1234567890ABCDEF
     assert affine(pa.ec_lincomb([(Pts[2], s7)] * 40)) == og1.multiply(g2, 40 * s7 % R_MOD)
     assert pa.ec_lincomb([(Pts[2], s7), (Pts[2], -s7)] * 9) is None

@@ -117,7 +117,7 @@ def comb_columns(h):
 
 
 def comb_table_bytes(n, h):
-    """csrc/msm.hip, msm_comb_bytes: the table and the XYZZ staging of its build (an eighth of the entries, at most 2^27)."""
+    """csrc/msm_comb.h, msm_comb_bytes: the table and the XYZZ staging of its build (an eighth of the entries, at most 2^27)."""
     half, bases = 1 << (h - 1), max(n // 8, 1)
     while bases > 1 and bases * half > 1 << 27:
         bases //= 2

@@ -4,7 +4,7 @@ with the product's flags and reports, per kernel, instruction count, VGPRs / spi
 the kernels whose body is one big loop (the MSM kernels) — the mix of the largest loops.  This is where DESIGN.md 3's
 "2 420 instructions per mixed addition" comes from.
 
-usage: python tools/instr_mix.py msm.hip [kernel-substring]      (writes nothing; prints a report)"""
+usage: python tools/instr_mix.py msm.hip [kernel-substring]      (writes nothing; prints a report; msm.hip compiles the kernels of msm_*.h)"""
 import collections
 import os
 import re
