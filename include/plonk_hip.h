@@ -344,6 +344,33 @@ int plonk_fr_ntt_distributed(plonk_comm* comm, const void* d_in, void* d_out, un
  * host (the verifier is off the prover hot path); no context needed.                          */
 int plonk_pairing_check(const uint8_t* g1_xy_le, const uint8_t* g1_is_identity, const uint8_t* g2_le, size_t count, int* out_ok);
 
+/* ---- batch verifier: N proofs of one circuit, one pairing check -------------------------------------------
+ * Replaces verify_proof (TESTING_verifier_DO_NOT_OPEN.py:39-163) for a batch.  Each proof's check is e(L_i, [x]_2) == e(R_i, [1]_2);
+ * with 128-bit weights rho_i the device returns sum rho_i L_i and sum rho_i R_i over a range and the caller asks
+ * plonk_pairing_check once: e(sum L, [x]_2) e(-sum R, [1]_2) == 1.  rho_i = the 16 bytes, read little-endian, of
+ * challenge_bytes(b"rho", 16) on a Merlin transcript b"plonk-batch-verify" after append_message(b"seed", seed) and
+ * append_message(b"index", i as 8 bytes little-endian).  A seed the prover can predict voids the soundness argument.
+ *   plonk_verifier_create   vk_xy_le = Qm, Ql, Qr, Qo, Qc, S1, S2, S3 as canonical x||y LE ((0,0) = identity)
+ *   plonk_verifier_load     proofs768 = batch x 768 B (plonk_prover_download's layout), public_le32 = [batch][n_public] canonical LE
+ *                           (a value not below r: PLONK_ERR_ARG).  Runs the per-proof work: status bytes, weighted scalars, the
+ *                           eleven scalar multiplications per proof, L_i and R_i (kept on the device).
+ *   plonk_verifier_load_prover   the same for the batch resident in a prover, without a trip through the host; `batch` must be the
+ *                           prover's resident batch (PLONK_ERR_STATE otherwise).
+ *   plonk_verifier_status   status[i]: 0 well-formed; bit 0 = a coordinate not below p or an evaluation not below r, bit 1 = a
+ *                           commitment is not on the curve, bit 2 = a commitment is the identity.  Such a proof has weight zero.
+ *   plonk_verifier_fold     sums over the proofs lo <= i < hi with status 0: L and R as canonical x||y LE + identity flags.  Any
+ *                           sub-range of a loaded batch can be folded; only range sums and the nine fixed-point products are redone.
+ *   plonk_g1_mul_many       count products k_j * P_j: points x||y canonical LE ((0,0) = identity), scalars canonical LE32.       */
+typedef struct plonk_verifier plonk_verifier;
+int plonk_verifier_create(plonk_ctx* ctx, unsigned log_n, const uint8_t vk_xy_le[8 * 64], size_t n_public, plonk_verifier** out);
+int plonk_verifier_destroy(plonk_verifier* v);
+int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs768, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]);
+int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch, const uint8_t seed[32]);
+int plonk_verifier_status(plonk_verifier* v, uint8_t* out_status);
+int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[64], uint8_t out_R[64], uint8_t out_is_identity[2]);
+int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_scalars_le32, size_t count, uint8_t* h_out_xy_le,
+                      uint8_t* h_out_is_identity);
+
 /* ---- Fiat-Shamir transcript (host) ----------------------------------------------------------------
  * Replaces `merlin.MerlinTranscript` (third-party) as subclassed by transcript.py:58-60:
  *   plonk_transcript_new              MerlinTranscript(label)             (prover.py:53 uses b"plonk")

@@ -102,6 +102,13 @@ SIGNATURES = {
     "plonk_comm_all_to_all": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "plonk_fr_ntt_distributed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int]),
     "plonk_pairing_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
+    "plonk_verifier_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, _u8p, ctypes.c_size_t, c_void_pp]),
+    "plonk_verifier_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "plonk_verifier_load": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t, _u8p]),
+    "plonk_verifier_load_prover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, _u8p]),
+    "plonk_verifier_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "plonk_verifier_fold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
+    "plonk_g1_mul_many": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]),
     "plonk_transcript_new": (ctypes.c_int, [_u8p, ctypes.c_size_t, c_void_pp]),
     "plonk_transcript_clone": (ctypes.c_int, [ctypes.c_void_p, c_void_pp]),
     "plonk_transcript_free": (ctypes.c_int, [ctypes.c_void_p]),

@@ -1337,3 +1337,7 @@ int prover_pack_device(plonk_prover* p, size_t B, int compressed, uint8_t* d_pro
 }
 
 plonk_ctx* prover_ctx(plonk_prover* p) { return p->ctx; }
+
+// ---- the batch verifier: kernels and plonk_verifier_* entry points (it reads the record layout, the device transcript and the
+// resident batch defined above)
+#include "verifier.h"

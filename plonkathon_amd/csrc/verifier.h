@@ -1,0 +1,620 @@
+// verifier.h — the batch verifier (plonk_verifier_*, plonk_g1_mul_many): N proofs of one circuit, one pairing check.
+//
+// Reference behaviour replaced: verify_proof of TESTING_verifier_DO_NOT_OPEN.py:39-163 (challenges :266-277) for a batch.  Every
+// proof's check is e(L_i, [x]_2) == e(R_i, [1]_2) with L_i, R_i in G1, so with random 128-bit weights rho_i the batch is accepted
+// iff e(sum rho_i L_i, [x]_2) == e(sum rho_i R_i, [1]_2): the device returns the two sums, the pairing stays on the host
+// (plonk_pairing_check).  Included from prover.hip, which owns the record layout, the device transcript (tc_*) and the resident
+// batch.  Three steps per loaded batch:
+//   verify_scalars_kernel   32 lanes per proof: well-formedness, transcript replay, the weighted scalars of the proof's terms
+//   g1_mul_many_kernel      one lane per (proof, term): k * P by double-and-add on the complete formulas of g1.h
+//   verify_fold_proof_kernel / verify_fold_kernel   L_i, R_i per proof (kept), then the sum over any range [lo, hi) + the nine
+//                           fixed-point products (their scalars are summed over the range in Fr first) -> two affine points
+#pragma once
+
+#define VF_OWN 11    // a_1, b_1, c_1, z_1, t_lo_1, t_mid_1, t_hi_1, W_z_1, W_zw_1 in R_i;  W_z_1, W_zw_1 in L_i
+#define VF_FIXED 9   // Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1
+#define VF_MALFORMED 1u
+#define VF_OFF_CURVE 2u
+#define VF_IDENTITY 4u
+
+template <class P> PLONK_HD bool vf_below_modulus(const uint32_t v[8]) {
+    bool lt = false, eq = true;
+#pragma unroll
+    for (int k = 7; k >= 0; k--)
+        if (eq && v[k] != P::mod(k)) {
+            lt = v[k] < P::mod(k);
+            eq = false;
+        }
+    return lt;
+}
+
+// y^2 == x^3 + 3 (Montgomery coordinates)
+PLONK_HD bool vf_on_curve(const Fq& x, const Fq& y) {
+    Fq three = fp_zero<FqParams>();
+    three.v[0] = 3;
+    return fp_eq(fp_sqr(y), fp_add(fp_mul(fp_sqr(x), x), fp_to_mont(three)));
+}
+
+// k * p for a canonical k < 2^254 and an affine p: left-to-right double-and-add on the complete formulas of g1.h.  The scalar
+// is shifted out of its top bit, so its words keep constant indices; the fences keep the scheduler from interleaving the
+// doubling's multiplications with the addition's (which multiplies the live registers).  Leading doublings of the identity
+// return at once.
+PLONK_DEV G1Xyzz g1_mul_affine(const G1Affine& p, Fr k) {
+    G1Xyzz acc = g1_xyzz_identity();
+    if (g1_affine_is_identity(p)) return acc;
+#pragma unroll
+    for (int i = 7; i > 0; i--) k.v[i] = (k.v[i] << 2) | (k.v[i - 1] >> 30);
+    k.v[0] <<= 2;
+#pragma unroll 1
+    for (int bit = 0; bit < 254; bit++) {
+        g1_dbl(acc);
+        PLONK_SCHED_FENCE();
+        if (k.v[7] >> 31) g1_madd<true>(acc, p);  // the rare acc == +-p exit as a call (g1.h:79-81)
+        PLONK_SCHED_FENCE();
+#pragma unroll
+        for (int i = 7; i > 0; i--) k.v[i] = (k.v[i] << 1) | (k.v[i - 1] >> 31);
+        k.v[0] <<= 1;
+    }
+    return acc;
+}
+
+// out[j] = scalars[j] * points[j]: points affine in Montgomery form ((0, 0) = identity), scalars canonical
+__global__ void __launch_bounds__(64) g1_mul_many_kernel(const G1Affine* points, const Fr* scalars, size_t count, G1Xyzz* out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    G1Affine p;
+    p.x = fp_load(&points[j].x);
+    p.y = fp_load(&points[j].y);
+    const G1Xyzz r = g1_mul_affine(p, fp_load(scalars + j));
+    fp_store(&out[j].x, r.x);
+    fp_store(&out[j].y, r.y);
+    fp_store(&out[j].zz, r.zz);
+    fp_store(&out[j].zzz, r.zzz);
+}
+
+PLONK_DEV G1Xyzz vf_load_xyzz(const G1Xyzz* p) {
+    G1Xyzz r;
+    r.x = fp_load(&p->x);
+    r.y = fp_load(&p->y);
+    r.zz = fp_load(&p->zz);
+    r.zzz = fp_load(&p->zzz);
+    return r;
+}
+PLONK_DEV void vf_store_xyzz(G1Xyzz* p, const G1Xyzz& r) {
+    fp_store(&p->x, r.x);
+    fp_store(&p->y, r.y);
+    fp_store(&p->zz, r.zz);
+    fp_store(&p->zzz, r.zzz);
+}
+
+// Per proof: 768-byte record + public inputs -> status byte, the eleven points in Montgomery form, their weighted scalars
+// (canonical: g1_mul_many_kernel reads bits) and the nine weighted fixed-point scalars (Montgomery: verify_fold_kernel sums them).
+// Lane layout of transcript_kernel: 32 lanes per proof, two proofs per workgroup, barriers uniform — a malformed proof replays the
+// transcript over its bytes as they are and its results are dropped (weight zero: identity points, zero scalars).
+//   init[0] = the transcript after Transcript(b"plonk"); init[1] = the weight transcript after the seed
+//   inv_tmp [B][max(n_public, 1)]: prefix products of the shared inversion (PI(zeta) and L0(zeta) need 1 / (zeta - w^i))
+struct VfShared {
+    TcShared tc;
+    uint32_t status;
+    uint32_t pad_[3];
+};
+struct VfDomain { Fr w, w_inv, n_inv; unsigned log_n; };
+__global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint8_t* proofs, const Fr* pub, size_t n_public, size_t B,
+                                                                      const MerlinState* init, ChallengeConsts cc, VfDomain dom, Fr* inv_tmp,
+                                                                      G1Affine* pts, Fr* own, Fr* fixed, uint8_t* status) {
+    __shared__ VfShared shared[2];
+    const unsigned grp = threadIdx.x / TC_LANES, lane = threadIdx.x % TC_LANES;
+    TcShared& sh = shared[grp].tc;
+    size_t b = (size_t)blockIdx.x * 2 + grp;
+    const bool live = b < B;
+    if (!live) b = B - 1;  // shadow the last proof so the barriers stay uniform; nothing is stored
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(proofs + b * 768);
+    if (lane == 0) shared[grp].status = 0;
+    __syncthreads();
+
+    // ---- well-formedness: lane k < 11 owns the point of term k (W_z_1, W_zw_1 twice), lanes 11..16 an evaluation
+    uint32_t bad = 0;
+    G1Affine P = g1_affine_identity();
+    if (lane < VF_OWN) {
+        const unsigned k = lane < 9 ? lane : lane - 2;
+        Fq x, y;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            x.v[i] = rec[16 * k + i];
+            y.v[i] = rec[16 * k + 8 + i];
+        }
+        if (!vf_below_modulus<FqParams>(x.v) || !vf_below_modulus<FqParams>(y.v)) bad = VF_MALFORMED;
+        else if (fp_is_zero(x) && fp_is_zero(y)) bad = VF_IDENTITY;  // the reference's transcript refuses None (transcript.py:62-67)
+        else {
+            P.x = fp_to_mont(x);
+            P.y = fp_to_mont(y);
+            if (!vf_on_curve(P.x, P.y)) bad = VF_OFF_CURVE;  // cofactor 1: on the curve is in the group
+        }
+    } else if (lane < VF_OWN + 6) {
+        uint32_t e[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) e[i] = rec[144 + 8 * (lane - VF_OWN) + i];
+        if (!vf_below_modulus<FrParams>(e)) bad = VF_MALFORMED;
+    }
+    if (bad) atomicOr(&shared[grp].status, bad);
+    __syncthreads();
+    const uint32_t st = shared[grp].status;
+
+    // ---- transcript replay (TESTING_verifier:266-277)
+    TcState t;
+    t.w = lane < 25 ? init[0].st[lane] : 0;
+    t.pos = init[0].pos;
+    t.pos_begin = init[0].pos_begin;
+    auto stage_points = [&](unsigned first, unsigned count) {  // big-endian x, y of `count` commitments to sh.msg
+        __syncthreads();  // earlier readers of sh.msg are done
+        if (lane < 2 * count) {
+            uint32_t v[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) v[i] = rec[16 * first + 8 * lane + i];
+            limbs_to_be32(v, sh.msg + 32 * lane);
+        }
+        __syncthreads();
+    };
+    auto absorb_point = [&](int k, const char* label, unsigned llen) {
+        tc_append_message(t, sh, lane, label, llen, sh.msg + 64 * k, 32);
+        tc_append_message(t, sh, lane, label, llen, sh.msg + 64 * k + 32, 32);
+    };
+    stage_points(0, 3);
+    absorb_point(0, "a_1", 3);
+    absorb_point(1, "b_1", 3);
+    absorb_point(2, "c_1", 3);
+    const Fr beta = tc_draw(t, sh, lane, cc, "beta", 4);
+    const Fr gamma = tc_draw(t, sh, lane, cc, "gamma", 5);
+    stage_points(3, 1);
+    absorb_point(0, "z_1", 3);
+    const Fr alpha = tc_draw(t, sh, lane, cc, "alpha", 5);
+    (void)tc_draw(t, sh, lane, cc, "fft_cofactor", 12);
+    stage_points(4, 3);
+    absorb_point(0, "t_lo_1", 6);
+    absorb_point(1, "t_mid_1", 7);
+    absorb_point(2, "t_hi_1", 6);
+    const Fr zeta = tc_draw(t, sh, lane, cc, "zeta", 4);
+    stage_points(9, 3);  // the six evaluations follow the nine points in the record, 32 bytes each: coordinates 18..23
+    tc_append_message(t, sh, lane, "a_eval", 6, sh.msg, 32);
+    tc_append_message(t, sh, lane, "b_eval", 6, sh.msg + 32, 32);
+    tc_append_message(t, sh, lane, "c_eval", 6, sh.msg + 64, 32);
+    tc_append_message(t, sh, lane, "s1_eval", 7, sh.msg + 96, 32);
+    tc_append_message(t, sh, lane, "s2_eval", 7, sh.msg + 128, 32);
+    tc_append_message(t, sh, lane, "z_shifted_eval", 14, sh.msg + 160, 32);
+    const Fr v = tc_draw(t, sh, lane, cc, "v", 1);
+    stage_points(7, 2);
+    absorb_point(0, "W_z_1", 5);
+    absorb_point(1, "W_zw_1", 6);
+    const Fr u = tc_draw(t, sh, lane, cc, "u", 1);
+
+    // ---- the weight: a clone of the seeded transcript, the proof's index, 16 challenge bytes read little-endian
+    TcState tr;
+    tr.w = lane < 25 ? init[1].st[lane] : 0;
+    tr.pos = init[1].pos;
+    tr.pos_begin = init[1].pos_begin;
+    __syncthreads();
+    if (lane < 8) sh.msg[lane] = (uint8_t)((uint64_t)b >> (8 * lane));
+    __syncthreads();
+    tc_append_message(tr, sh, lane, "index", 5, sh.msg, 8);
+    tc_frame(tr, sh, lane, "rho", 3, 16);
+    tc_begin_op(tr, sh, lane, STROBE_FLAG_I | STROBE_FLAG_A | STROBE_FLAG_C);
+    __syncthreads();
+    tc_squeeze(tr, sh, lane, sh.msg, 16);
+    __syncthreads();
+
+    if (!live) return;
+    if (lane < VF_OWN) {
+        if (st) P = g1_affine_identity();
+        fp_store(&pts[b * VF_OWN + lane].x, P.x);
+        fp_store(&pts[b * VF_OWN + lane].y, P.y);
+    }
+    if (lane != 0) return;
+    status[b] = (uint8_t)st;
+    Fr* o_own = own + b * VF_OWN;
+    Fr* o_fix = fixed + b * VF_FIXED;
+    if (st) {  // takes part in no fold
+        for (int k = 0; k < VF_OWN; k++) fp_store(o_own + k, fp_zero<FrParams>());
+        for (int k = 0; k < VF_FIXED; k++) fp_store(o_fix + k, fp_zero<FrParams>());
+        return;
+    }
+    const Fr one = fp_one<FrParams>();
+    Fr rho = fp_zero<FrParams>();
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        rho.v[i] = (uint32_t)sh.msg[4 * i] | ((uint32_t)sh.msg[4 * i + 1] << 8) | ((uint32_t)sh.msg[4 * i + 2] << 16) | ((uint32_t)sh.msg[4 * i + 3] << 24);
+    rho = fp_to_mont(rho);
+    Fr ev[6];
+#pragma unroll
+    for (int e = 0; e < 6; e++) {
+        Fr x;
+#pragma unroll
+        for (int i = 0; i < 8; i++) x.v[i] = rec[144 + 8 * e + i];
+        ev[e] = fp_to_mont(x);
+    }
+    const Fr a = ev[0], bb = ev[1], c = ev[2], s1 = ev[3], s2 = ev[4], zw = ev[5];
+    Fr zn = zeta;
+    for (unsigned i = 0; i < dom.log_n; i++) zn = fp_sqr(zn);
+    const Fr zh = fp_sub(zn, one);
+    // 1 / (zeta - w^i), i < m, by ONE inversion (Montgomery's trick; a zero denominator inverts to zero, as the reference's field does)
+    const size_t m = n_public ? n_public : 1;
+    Fr* tmp = inv_tmp + b * m;
+    Fr run = one, wi = one, w_last = one;
+    for (size_t i = 0; i < m; i++) {
+        Fr d = fp_sub(zeta, wi);
+        if (fp_is_zero(d)) d = one;
+        fp_store(tmp + i, run);
+        run = fp_mul(run, d);
+        w_last = wi;
+        wi = fp_mul(wi, dom.w);
+    }
+    Fr inv = fp_inv(run), sum = fp_zero<FrParams>(), inv0 = fp_zero<FrParams>();
+    wi = w_last;
+    for (size_t i = m; i-- > 0;) {
+        const Fr d = fp_sub(zeta, wi);
+        Fr inv_i = fp_zero<FrParams>();
+        if (!fp_is_zero(d)) {
+            inv_i = fp_mul(inv, fp_load(tmp + i));
+            inv = fp_mul(inv, d);
+        }
+        if (i < n_public) sum = fp_add(sum, fp_mul(fp_mul(fp_load(pub + b * n_public + i), wi), inv_i));
+        if (i == 0) inv0 = inv_i;
+        wi = fp_mul(wi, dom.w_inv);
+    }
+    const Fr zhn = fp_mul(zh, dom.n_inv);
+    const Fr pi = fp_neg(fp_mul(zhn, sum));  // PI = sum (-public_i) L_i(zeta), poly.py:181-195
+    const Fr l0 = fp_mul(zhn, inv0);         // L0 = Z_H / (n (zeta - 1))
+    const Fr bz = fp_mul(beta, zeta);
+    const Fr k1 = fp_mul(fp_mul(fp_add(fp_add(a, bz), gamma), fp_add(fp_add(bb, fp_dbl(bz)), gamma)), fp_add(fp_add(c, fp_mul3(bz)), gamma));
+    const Fr e12 = fp_mul(fp_add(fp_add(a, fp_mul(beta, s1)), gamma), fp_add(fp_add(bb, fp_mul(beta, s2)), gamma));
+    const Fr l0a2 = fp_mul(l0, fp_sqr(alpha));
+    const Fr ae12zw = fp_mul(fp_mul(alpha, e12), zw);
+    const Fr r0 = fp_sub(fp_sub(pi, l0a2), fp_mul(ae12zw, fp_add(c, gamma)));
+    const Fr v2 = fp_sqr(v), v3 = fp_mul(v2, v), v4 = fp_sqr(v2), v5 = fp_mul(v4, v);
+    Fr open = fp_add(fp_mul(v, a), fp_mul(v2, bb));
+    open = fp_add(open, fp_add(fp_mul(v3, c), fp_mul(v4, s1)));
+    open = fp_add(open, fp_add(fp_mul(v5, s2), fp_mul(u, zw)));
+    const Fr nzh = fp_neg(zh);
+    const Fr s_own[VF_OWN] = {v, v2, v3, fp_add(fp_add(fp_mul(alpha, k1), l0a2), u), nzh, fp_mul(nzh, zn), fp_mul(nzh, fp_sqr(zn)),
+                              zeta, fp_mul(fp_mul(u, zeta), dom.w), one, u};
+    const Fr s_fix[VF_FIXED] = {fp_mul(a, bb), a, bb, c, one, v4, v5, fp_neg(fp_mul(ae12zw, beta)), fp_sub(r0, open)};
+#pragma unroll
+    for (int k = 0; k < VF_OWN; k++) fp_store(o_own + k, fp_from_mont(fp_mul(s_own[k], rho)));
+#pragma unroll
+    for (int k = 0; k < VF_FIXED; k++) fp_store(o_fix + k, fp_mul(s_fix[k], rho));
+}
+
+// lr[2 b] = L_b = products 9, 10 of proof b; lr[2 b + 1] = R_b = products 0..8.  One lane per (proof, side).
+__global__ void __launch_bounds__(64) verify_fold_proof_kernel(const G1Xyzz* prod, size_t B, G1Xyzz* lr) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 2 * B) return;
+    const size_t b = j >> 1;
+    const unsigned first = (j & 1) ? 0 : 9, count = (j & 1) ? 9 : 2;
+    G1Xyzz acc = vf_load_xyzz(prod + b * VF_OWN + first);
+#pragma unroll 1
+    for (unsigned k = 1; k < count; k++) g1_add(acc, vf_load_xyzz(prod + b * VF_OWN + first + k));
+    vf_store_xyzz(lr + j, acc);
+}
+
+// One workgroup: sum of L_b, of R_b and of the nine fixed-point scalars over lo <= b < hi (tree through LDS), the nine fixed-point
+// products, R += them, both sums to affine.  out_xy = L.x, L.y, R.x, R.y canonical; out_flags[side] = 1 for the identity.
+#define VF_FOLD_THREADS 256
+__global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_kernel(const G1Xyzz* lr, const Fr* fixed, const uint8_t* status, size_t lo, size_t hi,
+                                                                      const G1Affine* bases, Fq* out_xy, uint8_t* out_flags) {
+    __shared__ G1Xyzz red[VF_FOLD_THREADS];
+    __shared__ Fr fred[VF_FOLD_THREADS];
+    __shared__ G1Xyzz total[2];
+    __shared__ Fr fsum[VF_FIXED];
+    const unsigned tid = threadIdx.x;
+#pragma unroll 1
+    for (unsigned side = 0; side < 2; side++) {
+        G1Xyzz acc = g1_xyzz_identity();
+#pragma unroll 1
+        for (size_t b = lo + tid; b < hi; b += VF_FOLD_THREADS)
+            if (!status[b]) g1_add(acc, vf_load_xyzz(lr + 2 * b + side));
+        red[tid] = acc;
+        __syncthreads();
+#pragma unroll 1
+        for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
+            if (tid < s) {
+                G1Xyzz x = red[tid];
+                g1_add(x, red[tid + s]);
+                red[tid] = x;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) total[side] = red[0];
+        __syncthreads();
+    }
+#pragma unroll 1
+    for (unsigned k = 0; k < VF_FIXED; k++) {
+        Fr acc = fp_zero<FrParams>();
+        for (size_t b = lo + tid; b < hi; b += VF_FOLD_THREADS)
+            if (!status[b]) acc = fp_add(acc, fp_load(fixed + b * VF_FIXED + k));
+        fred[tid] = acc;
+        __syncthreads();
+        for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
+            if (tid < s) fred[tid] = fp_add(fred[tid], fred[tid + s]);
+            __syncthreads();
+        }
+        if (tid == 0) fsum[k] = fred[0];
+        __syncthreads();
+    }
+    if (tid < VF_FIXED) {
+        G1Affine p;
+        p.x = fp_load(&bases[tid].x);
+        p.y = fp_load(&bases[tid].y);
+        red[tid] = g1_mul_affine(p, fp_from_mont(fsum[tid]));
+    }
+    __syncthreads();
+    if (tid < 2) {
+        G1Xyzz acc = total[tid];
+        if (tid == 1)
+#pragma unroll 1
+            for (unsigned k = 0; k < VF_FIXED; k++) g1_add(acc, red[k]);
+        const G1Affine r = g1_to_affine(acc);
+        fp_store(out_xy + 2 * tid, fp_from_mont(r.x));
+        fp_store(out_xy + 2 * tid + 1, fp_from_mont(r.y));
+        out_flags[tid] = g1_is_identity(acc) ? 1 : 0;
+    }
+}
+
+// plonk_g1_mul_many's marshalling: canonical points -> Montgomery form with the range / curve tests, products -> canonical affine
+__global__ void g1_mul_many_in_kernel(Fq* xy, const Fr* scalars, size_t count, uint32_t* bad) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const Fq x = fp_load(xy + 2 * j), y = fp_load(xy + 2 * j + 1);
+    const Fr k = fp_load(scalars + j);
+    if (!vf_below_modulus<FqParams>(x.v) || !vf_below_modulus<FqParams>(y.v) || !vf_below_modulus<FrParams>(k.v)) {
+        atomicOr(bad, 1u);
+        fp_store(xy + 2 * j, fp_zero<FqParams>());
+        fp_store(xy + 2 * j + 1, fp_zero<FqParams>());
+        return;
+    }
+    if (fp_is_zero(x) && fp_is_zero(y)) return;
+    const Fq xm = fp_to_mont(x), ym = fp_to_mont(y);
+    if (!vf_on_curve(xm, ym)) atomicOr(bad, 2u);
+    fp_store(xy + 2 * j, xm);
+    fp_store(xy + 2 * j + 1, ym);
+}
+__global__ void g1_mul_many_out_kernel(const G1Xyzz* prod, size_t count, Fq* out_xy, uint8_t* flags) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const G1Xyzz p = vf_load_xyzz(prod + j);
+    const G1Affine r = g1_to_affine(p);
+    fp_store(out_xy + 2 * j, fp_from_mont(r.x));
+    fp_store(out_xy + 2 * j + 1, fp_from_mont(r.y));
+    flags[j] = g1_is_identity(p) ? 1 : 0;
+}
+
+// ================================================================================================
+// host side
+struct plonk_verifier {
+    plonk_ctx* ctx;
+    unsigned log_n;
+    size_t n_public;
+    VfDomain dom;
+    ChallengeConsts chal;
+    MerlinState h_init[2];   // [0] Transcript(b"plonk"), [1] the weight transcript after the seed of the last load
+    MerlinState* d_init;
+    G1Affine* d_bases;       // [9] Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1 (Montgomery)
+    size_t cap, batch;       // allocated / loaded proofs
+    uint8_t* d_proofs;       // [B][768]
+    Fr* d_pub;               // [B][n_public] Montgomery
+    Fr* d_inv_tmp;           // [B][max(n_public, 1)]
+    G1Affine* d_pts;         // [B][11]
+    Fr* d_own;               // [B][11] canonical
+    Fr* d_fixed;             // [B][9] Montgomery
+    G1Xyzz* d_prod;          // [B][11]
+    G1Xyzz* d_lr;            // [B][2]  L_b, R_b: any sub-range folds again from these
+    uint8_t* d_status;       // [B]
+    Fq* d_out;               // [4] + 2 flag bytes behind them
+    hipEvent_t ev;           // the prover's pack is done (plonk_verifier_load_prover)
+};
+
+static void verifier_free_batch(plonk_verifier* v) {
+    void* bufs[] = {v->d_proofs, v->d_pub, v->d_inv_tmp, v->d_pts, v->d_own, v->d_fixed, v->d_prod, v->d_lr, v->d_status};
+    for (void* q : bufs)
+        if (q) hipFree(q);
+    v->d_proofs = v->d_status = nullptr;
+    v->d_pub = v->d_inv_tmp = v->d_own = v->d_fixed = nullptr;
+    v->d_pts = nullptr;
+    v->d_prod = v->d_lr = nullptr;
+    v->cap = v->batch = 0;
+}
+
+static int verifier_ensure(plonk_verifier* v, size_t B) {
+    if (B <= v->cap) return PLONK_OK;
+    PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));
+    verifier_free_batch(v);
+    const size_t m = v->n_public ? v->n_public : 1;
+    PLONK_TRY(dev_alloc((void**)&v->d_proofs, B * 768));
+    PLONK_TRY(dev_alloc((void**)&v->d_pub, B * m * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_inv_tmp, B * m * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_pts, B * VF_OWN * sizeof(G1Affine)));
+    PLONK_TRY(dev_alloc((void**)&v->d_own, B * VF_OWN * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_fixed, B * VF_FIXED * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_prod, B * VF_OWN * sizeof(G1Xyzz)));
+    PLONK_TRY(dev_alloc((void**)&v->d_lr, B * 2 * sizeof(G1Xyzz)));
+    PLONK_TRY(dev_alloc((void**)&v->d_status, B));
+    v->cap = B;
+    return PLONK_OK;
+}
+
+// the proofs and public inputs of `B` proofs are in place on the verifier's stream: weights, scalars, products, L_b and R_b
+static int verifier_run(plonk_verifier* v, size_t B, const uint8_t seed[32]) {
+    plonk_ctx* ctx = v->ctx;
+    hipStream_t s = ctx->stream;
+    merlin_init(v->h_init[1], (const uint8_t*)"plonk-batch-verify", 18);
+    merlin_append_message(v->h_init[1], (const uint8_t*)"seed", 4, seed, 32);
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_init, v->h_init, sizeof v->h_init, hipMemcpyHostToDevice, s));
+    PLONK_LAUNCH(verify_scalars_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, s, (const uint8_t*)v->d_proofs, (const Fr*)v->d_pub,
+                 v->n_public, B, (const MerlinState*)v->d_init, v->chal, v->dom, v->d_inv_tmp, v->d_pts, v->d_own, v->d_fixed, v->d_status);
+    const size_t count = B * VF_OWN;
+    PLONK_LAUNCH(g1_mul_many_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, (const G1Affine*)v->d_pts, (const Fr*)v->d_own, count,
+                 v->d_prod);
+    PLONK_LAUNCH(verify_fold_proof_kernel, dim3((unsigned)((2 * B + 63) / 64)), dim3(64), 0, s, (const G1Xyzz*)v->d_prod, B, v->d_lr);
+    PLONK_CHECK_HIP(hipGetLastError());
+    PLONK_CHECK_HIP(hipStreamSynchronize(s));
+    v->batch = B;
+    return PLONK_OK;
+}
+
+static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned log_n, const uint8_t* vk_xy_le, size_t n_public) {
+    v->ctx = ctx;
+    v->log_n = log_n;
+    v->n_public = n_public;
+    v->dom.log_n = log_n;
+    v->dom.w = host_root_of_unity(log_n, false);
+    v->dom.w_inv = host_root_of_unity(log_n, true);
+    v->dom.n_inv = fp_inv(host_fr_u64((uint64_t)1 << log_n));
+    {   // transcript_kernel's challenge constants (prover_init)
+        Fr t = fp_zero<FrParams>();
+        t.v[4] = 1;
+        t = fp_to_mont(t);
+        const Fr two256 = fp_mul(t, t);
+        for (int i = 0; i < 8; i++) v->chal.c[0].v[i] = FrParams::r2(i);
+        for (int j = 1; j < 8; j++) v->chal.c[j] = fp_mul(v->chal.c[j - 1], two256);
+    }
+    merlin_init(v->h_init[0], (const uint8_t*)"plonk", 5);
+    v->h_init[1] = v->h_init[0];
+    G1Affine bases[VF_FIXED];
+    for (int k = 0; k < 8; k++) {
+        const uint8_t* q = vk_xy_le + 64 * k;
+        PLONK_REQUIRE(le32_below_modulus(q, true) && le32_below_modulus(q + 32, true), PLONK_ERR_ARG, "verification key point %d: a coordinate is not below p", k);
+        Fq x, y;
+        memcpy(x.v, q, 32);
+        memcpy(y.v, q + 32, 32);
+        bases[k].x = fp_to_mont(x);
+        bases[k].y = fp_to_mont(y);
+        PLONK_REQUIRE(g1_affine_is_identity(bases[k]) || vf_on_curve(bases[k].x, bases[k].y), PLONK_ERR_ARG, "verification key point %d is not on the curve", k);
+    }
+    bases[8].x = fp_one<FqParams>();  // G1 = (1, 2)
+    bases[8].y = fp_dbl(bases[8].x);
+    PLONK_TRY(dev_alloc((void**)&v->d_init, sizeof v->h_init));
+    PLONK_TRY(dev_alloc((void**)&v->d_bases, sizeof bases));
+    PLONK_TRY(dev_alloc((void**)&v->d_out, 4 * sizeof(Fq) + 16));
+    PLONK_CHECK_HIP(hipEventCreate(&v->ev));
+    PLONK_CHECK_HIP(hipMemcpy(v->d_bases, bases, sizeof bases, hipMemcpyHostToDevice));
+    return PLONK_OK;
+}
+
+extern "C" {
+
+int plonk_verifier_create(plonk_ctx* ctx, unsigned log_n, const uint8_t vk_xy_le[8 * 64], size_t n_public, plonk_verifier** out) {
+    PLONK_REQUIRE(ctx && vk_xy_le && out, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(ctx);
+    PLONK_REQUIRE(log_n >= 1 && log_n <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "group_order 2^%u out of range", log_n);
+    PLONK_REQUIRE(n_public <= ((size_t)1 << log_n), PLONK_ERR_ARG, "more public inputs than rows");
+    plonk_verifier* v = new plonk_verifier();
+    memset((void*)v, 0, sizeof *v);
+    const int rc = verifier_init(v, ctx, log_n, vk_xy_le, n_public);
+    if (rc != PLONK_OK) {
+        plonk_verifier_destroy(v);
+        return rc;
+    }
+    *out = v;
+    return PLONK_OK;
+}
+
+int plonk_verifier_destroy(plonk_verifier* v) {
+    if (!v) return PLONK_OK;
+    if (v->ctx) {
+        plonk_use_device(v->ctx->device);
+        hipStreamSynchronize(v->ctx->stream);
+    }
+    verifier_free_batch(v);
+    void* bufs[] = {v->d_init, v->d_bases, v->d_out};
+    for (void* q : bufs)
+        if (q) hipFree(q);
+    if (v->ev) hipEventDestroy(v->ev);
+    delete v;
+    return PLONK_OK;
+}
+
+int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs768, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && proofs768 && batch && seed && (public_le32 || !v->n_public), PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(v->ctx);
+    v->batch = 0;  // until the new batch is in place
+    PLONK_TRY(verifier_ensure(v, batch));
+    if (v->n_public) PLONK_TRY(plonk_fr_upload(v->ctx, v->d_pub, public_le32, batch * v->n_public));  // a value not below r: PLONK_ERR_ARG
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_proofs, proofs768, batch * 768, hipMemcpyHostToDevice, v->ctx->stream));
+    return verifier_run(v, batch, seed);
+}
+
+int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && p && batch && seed, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(p->ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->ctx->device, v->ctx->device);
+    PLONK_REQUIRE(p->log_n == v->log_n && p->n_public == v->n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %zu)",
+                  p->log_n, p->n_public, v->log_n, v->n_public);
+    PLONK_REQUIRE(batch == p->resident_b, PLONK_ERR_STATE, "verify: batch %zu, but %zu proofs are resident in the prover", batch, p->resident_b);
+    PLONK_ENTER(v->ctx);
+    v->batch = 0;
+    PLONK_TRY(verifier_ensure(v, batch));
+    // on the prover's stream, behind its five rounds.  The PROVER's status bytes land in d_status and are discarded on purpose
+    // (verify_scalars_kernel overwrites them): a proof its prover flagged is verified like any other, and rejected
+    PLONK_TRY(prover_pack_device(p, batch, 0, v->d_proofs, v->d_status, v->ev));
+    PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->ev, 0));
+    if (v->n_public)
+        PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->pub, batch * v->n_public * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
+    return verifier_run(v, batch, seed);
+}
+
+int plonk_verifier_status(plonk_verifier* v, uint8_t* out_status) {
+    PLONK_REQUIRE(v && out_status, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v->batch, PLONK_ERR_STATE, "no batch is loaded");
+    PLONK_ENTER(v->ctx);
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_status, v->d_status, v->batch, hipMemcpyDeviceToHost, v->ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));
+    return PLONK_OK;
+}
+
+int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[64], uint8_t out_R[64], uint8_t out_is_identity[2]) {
+    PLONK_REQUIRE(v && out_L && out_R && out_is_identity, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v->batch, PLONK_ERR_STATE, "no batch is loaded");
+    PLONK_REQUIRE(lo <= hi && hi <= v->batch, PLONK_ERR_ARG, "fold: range [%zu, %zu) of a batch of %zu", lo, hi, v->batch);
+    PLONK_ENTER(v->ctx);
+    hipStream_t s = v->ctx->stream;
+    uint8_t* d_flags = reinterpret_cast<uint8_t*>(v->d_out + 4);
+    PLONK_LAUNCH(verify_fold_kernel, dim3(1), dim3(VF_FOLD_THREADS), 0, s, (const G1Xyzz*)v->d_lr, (const Fr*)v->d_fixed, (const uint8_t*)v->d_status, lo, hi,
+                 (const G1Affine*)v->d_bases, v->d_out, d_flags);
+    PLONK_CHECK_HIP(hipGetLastError());
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_L, v->d_out, 64, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_R, v->d_out + 2, 64, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_is_identity, d_flags, 2, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipStreamSynchronize(s));
+    return PLONK_OK;
+}
+
+int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_scalars_le32, size_t count, uint8_t* h_out_xy_le, uint8_t* h_out_is_identity) {
+    PLONK_REQUIRE(ctx && (count == 0 || (h_xy_le && h_scalars_le32 && h_out_xy_le && h_out_is_identity)), PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(ctx);
+    if (!count) return PLONK_OK;
+    void* buf;
+    PLONK_TRY(ctx_scratch(ctx, 3, count * (64 + 32 + 128 + 64 + 1) + 64, &buf));
+    uint8_t* base = (uint8_t*)buf;
+    Fq* d_xy = (Fq*)base;
+    Fr* d_k = (Fr*)(base + count * 64);
+    G1Xyzz* d_prod = (G1Xyzz*)(base + count * 96);
+    Fq* d_out = (Fq*)(base + count * 224);
+    uint32_t* d_bad = (uint32_t*)(base + count * 288);
+    uint8_t* d_flags = base + count * 288 + 16;
+    hipStream_t s = ctx->stream;
+    const dim3 grid((unsigned)((count + 63) / 64));
+    PLONK_CHECK_HIP(hipMemcpyAsync(d_xy, h_xy_le, count * 64, hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(d_k, h_scalars_le32, count * 32, hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipMemsetAsync(d_bad, 0, 4, s));
+    PLONK_LAUNCH(g1_mul_many_in_kernel, grid, dim3(64), 0, s, d_xy, (const Fr*)d_k, count, d_bad);
+    PLONK_LAUNCH(g1_mul_many_kernel, grid, dim3(64), 0, s, (const G1Affine*)d_xy, (const Fr*)d_k, count, d_prod);
+    PLONK_LAUNCH(g1_mul_many_out_kernel, grid, dim3(64), 0, s, (const G1Xyzz*)d_prod, count, d_out, d_flags);
+    PLONK_CHECK_HIP(hipGetLastError());
+    uint32_t bad = 0;
+    PLONK_CHECK_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(h_out_xy_le, d_out, count * 64, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(h_out_is_identity, d_flags, count, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipStreamSynchronize(s));
+    PLONK_REQUIRE(!(bad & 1), PLONK_ERR_ARG, "a coordinate is not below p, or a scalar not below r");
+    PLONK_REQUIRE(!(bad & 2), PLONK_ERR_ARG, "a point is not on the curve");
+    return PLONK_OK;
+}
+
+}  // extern "C"

@@ -201,6 +201,14 @@ class VerificationKey:
         # e(lhs, [x]_2) == e(rhs, [1]_2)
         return pairing_check([(lhs, self.X_2), (_g1_neg(rhs), G2)])
 
+    def verify_batch(self, proofs, publics, seed=None) -> bool:
+        """Every proof of a batch (at least one) under ONE pairing check (verify.BatchVerifier.verify; `publics`: one row per
+        proof).  Builds and frees a device verifier per call: keep a BatchVerifier when checking batch after batch."""
+        from .verify import BatchVerifier
+
+        publics = [list(row) for row in publics]
+        return BatchVerifier(self, len(publics[0]) if publics else 0).verify(proofs, publics, seed)
+
     # TESTING_verifier_DO_NOT_OPEN.py:166-264: the two opening checks separately.  e(Y, [1]_2) == e(W, [x]_2 - z [1]_2) is
     # asked as e(Y + z W, [1]_2) e(-W, [x]_2) == 1, so no arithmetic in G2 is needed.
     def verify_proof_unoptimized(self, group_order: int, pf, public=[]) -> bool:

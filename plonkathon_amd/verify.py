@@ -1,0 +1,185 @@
+"""`BatchVerifier` — N proofs of one circuit checked with one pairing product.
+
+The reference verifies one proof per call (TESTING_verifier_DO_NOT_OPEN.py:39-163): e(L, [x]_2) == e(R, [1]_2) with L, R in G1.
+For a batch the device computes every proof's L_i and R_i (transcript replay, field arithmetic and eleven scalar
+multiplications per proof: plonk_verifier_* in include/plonk_hip.h), folds them under random 128-bit weights rho_i, and the host
+asks `pairing_check` once: e(sum rho_i L_i, [x]_2) == e(sum rho_i R_i, [1]_2).  Honest batches always pass; a batch holding a bad
+proof passes with probability about 2^-128.
+"""
+import ctypes
+import os
+
+from ._lib import check
+from .backend import get_context
+from .field import Fq
+from .kzg import G2, _g1_neg, pairing_check
+from .plonk import Proof
+from .polynomial import _log2_exact
+
+STATUS_MALFORMED, STATUS_OFF_CURVE, STATUS_IDENTITY = 1, 2, 4
+_NOT_BELOW_P = b"\xff" * 32  # stands in for a coordinate the compressed encoding could not give: status bit 0 on the device
+
+
+def _point_bytes(pt):
+    return bytes(64) if pt is None else int(pt[0]).to_bytes(32, "little") + int(pt[1]).to_bytes(32, "little")
+
+
+class BatchVerifier:
+    def __init__(self, vk, n_public: int, ctx=None):
+        """`vk`: the VerificationKey of `Setup.verification_key(...)`; `n_public`: public inputs per proof."""
+        self.vk, self.n_public = vk, int(n_public)
+        self.ctx = ctx or get_context()
+        self.status, self.pairing_checks = b"", 0
+        self._batch = 0
+        blob = b"".join(_point_bytes(p) for p in (vk.Qm, vk.Ql, vk.Qr, vk.Qo, vk.Qc, vk.S1, vk.S2, vk.S3))
+        self._h = ctypes.c_void_p()
+        check(self.ctx.L.plonk_verifier_create(self.ctx.handle, _log2_exact(vk.group_order), blob, self.n_public, ctypes.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h and self.ctx.handle:
+                self.ctx.L.plonk_verifier_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    # ---- inputs ---------------------------------------------------------------------------------
+    def _records(self, proofs, B):
+        """768-byte records (plonk_prover_download's layout) from 768-byte records, 480-byte compressed records or Proof objects."""
+        if isinstance(proofs, (bytes, bytearray, memoryview)):
+            proofs = bytes(proofs)
+            if len(proofs) == 768 * B:
+                return proofs
+            assert len(proofs) == 480 * B, "proofs: %d bytes are neither %d records of 768 nor of 480 bytes" % (len(proofs), B)
+            return self._decompress(proofs, B)
+        proofs = list(proofs)
+        assert len(proofs) == B, "%d proofs, %d rows of public inputs" % (len(proofs), B)
+        out = []
+        for p in proofs:
+            f = p.flatten()
+            out.append(b"".join(_point_bytes(f[k]) for k in Proof._POINTS) + b"".join(int(f[k]).to_bytes(32, "little") for k in Proof._SCALARS))
+        return b"".join(out)
+
+    def _decompress(self, blob, B):
+        pts = b"".join(blob[480 * i : 480 * i + 288] for i in range(B))
+        xy = ctypes.create_string_buffer(64 * 9 * B)
+        st = ctypes.create_string_buffer(9 * B)
+        check(self.ctx.L.plonk_g1_decompress(self.ctx.handle, pts, 9 * B, xy, st))
+        xy, st = xy.raw, st.raw
+        out = []
+        for i in range(B):
+            for k in range(9):
+                j = 9 * i + k
+                if st[j] == 1:  # malformed encoding: status bit 0
+                    out.append(_NOT_BELOW_P + _NOT_BELOW_P)
+                elif st[j] == 2:  # x^3 + 3 is not a square, 1 is: (x, 1) is off the curve, status bit 1
+                    x = int.from_bytes(pts[32 * j : 32 * j + 32], "big") & ((1 << 254) - 1)
+                    out.append(x.to_bytes(32, "little") + (1).to_bytes(32, "little"))
+                else:
+                    out.append(xy[64 * j : 64 * j + 64])
+            out.append(b"".join(blob[480 * i + 288 + 32 * e : 480 * i + 320 + 32 * e][::-1] for e in range(6)))  # big-endian there
+        return b"".join(out)
+
+    def _publics(self, publics):
+        rows = []
+        for row in publics:
+            row = [int(x) for x in row]
+            assert len(row) == self.n_public, "a row of %d public inputs, the circuit has %d" % (len(row), self.n_public)
+            assert all(0 <= x < (1 << 256) for x in row), "a public input is not a canonical Fr value"
+            rows.append(b"".join(x.to_bytes(32, "little") for x in row))
+        return b"".join(rows)
+
+    @staticmethod
+    def _seed(seed):
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        assert len(seed) == 32, "seed: 32 bytes"
+        return seed
+
+    def load(self, proofs, publics, seed=None):
+        """Per-proof work on the device: status bytes, weighted scalars, scalar multiplications, L_i and R_i."""
+        publics = list(publics)
+        B = len(publics)
+        pub = self._publics(publics)
+        rec = self._records(proofs, B)
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load(self._h, rec, pub if self.n_public else None, B, self._seed(seed)))
+        self._loaded(B)
+
+    def load_prover(self, batch_prover, B=None, seed=None):
+        """The same for the batch resident in a BatchProver (after run()): the proofs never leave the device."""
+        B = batch_prover._resident if B is None else B
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load_prover(self._h, batch_prover._h, B, self._seed(seed)))
+        self._loaded(B)
+
+    def _loaded(self, B):
+        st = ctypes.create_string_buffer(B)
+        check(self.ctx.L.plonk_verifier_status(self._h, st))
+        self.status, self._batch, self.pairing_checks = st.raw[:B], B, 0
+
+    # ---- folds and verdicts ---------------------------------------------------------------------
+    def fold(self, lo, hi):
+        """(sum rho_i L_i, sum rho_i R_i) over the well-formed proofs lo <= i < hi of the loaded batch; None = identity."""
+        L, R, fl = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64), ctypes.create_string_buffer(2)
+        check(self.ctx.L.plonk_verifier_fold(self._h, lo, hi, L, R, fl))
+
+        def pt(buf, flag):
+            return None if flag else (Fq(int.from_bytes(buf.raw[:32], "little")), Fq(int.from_bytes(buf.raw[32:64], "little")))
+
+        return pt(L, fl.raw[0]), pt(R, fl.raw[1])
+
+    def check_pairing(self, L, R) -> bool:
+        """e(L, [x]_2) == e(R, [1]_2) for the two points of a fold: the one pairing product of a batch (host CPU)."""
+        self.pairing_checks += 1
+        return pairing_check([(L, self.vk.X_2), (_g1_neg(R), G2)])
+
+    def _check(self, lo, hi):
+        return self.check_pairing(*self.fold(lo, hi))
+
+    def _verdict(self):
+        return all(s == 0 for s in self.status) and self._check(0, self._batch)
+
+    def _verdicts(self):
+        B = self._batch
+        res = [s == 0 for s in self.status]
+        if self._check(0, B):
+            return res
+
+        def split(lo, hi):  # the fold over [lo, hi) is known to fail
+            if hi - lo == 1:
+                res[lo] = False
+                return
+            mid = (lo + hi) // 2
+            if self._check(lo, mid):
+                split(mid, hi)  # the failure is on the right: no check needed to know it
+                return
+            split(lo, mid)
+            if not self._check(mid, hi):
+                split(mid, hi)
+
+        split(0, B)
+        return res
+
+    def verify(self, proofs, publics, seed=None) -> bool:
+        """True iff every proof is well-formed and the fold over the whole batch passes the pairing check.  `proofs`: bytes of
+        768-byte records, bytes of 480-byte compressed records (BatchProver.download_compressed) or a list of Proof objects;
+        `publics`: one row of public inputs per proof (at least one proof: an empty batch is the library's "bad argument").
+        `seed`: 32 bytes the weights are derived from; a seed the prover can
+        predict voids the soundness argument, so leave it None (os.urandom) outside tests and reproducible runs."""
+        self.load(proofs, publics, seed)
+        return self._verdict()
+
+    def verify_each(self, proofs, publics, seed=None):
+        """One verdict per proof.  The whole batch first; only if that fails, bisection by folds over sub-ranges (same weights,
+        nothing recomputed on the device but range sums): at most 2 k ceil(log2 B) + 1 pairing checks for k bad proofs."""
+        self.load(proofs, publics, seed)
+        return self._verdicts()
+
+    def verify_prover(self, batch_prover, B=None, seed=None) -> bool:
+        """verify() for the batch resident in `batch_prover` (after run()), without a trip through the host."""
+        self.load_prover(batch_prover, B, seed)
+        return self._verdict()
+
+    def verify_each_prover(self, batch_prover, B=None, seed=None):
+        self.load_prover(batch_prover, B, seed)
+        return self._verdicts()
