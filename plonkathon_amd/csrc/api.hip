@@ -94,12 +94,7 @@ Fr fr_from_le32(const uint8_t* b) {
 bool le32_below_modulus(const uint8_t* b, bool fq) {
     uint32_t v[8];
     memcpy(v, b, 32);
-    for (int i = 7; i >= 0; i--) {
-        uint32_t m = fq ? FqParams::mod(i) : FrParams::mod(i);
-        if (v[i] < m) return true;
-        if (v[i] > m) return false;
-    }
-    return false;
+    return fq ? fp_below_modulus<FqParams>(v) : fp_below_modulus<FrParams>(v);
 }
 
 // .ptau coordinates are Montgomery residues with R = 2^256 (setup.py:39-40); ours use R = 2^PLONK_MONT_BITS.

@@ -1,5 +1,5 @@
 // comm.hip — everything that crosses xGMI, RCCL behind the C-ABI:
-//   * the one collective of the prover path: gathering the finished proofs (768 bytes each: 9 affine G1 + 6 Fr) of
+//   * the one collective of the prover path: gathering the finished proofs (records of 9 affine G1 + 6 Fr) of
 //     independently proving GPUs (SURVEY.md §8(b) `plonk_gather_results`, §8(e)), plus a barrier and a max-reduction
 //     for the benchmark clock;
 //   * the transpose step of a transform split across GPUs (`plonk_comm_all_to_all`, `plonk_fr_ntt_distributed`,
@@ -328,7 +328,7 @@ int plonk_gather_results(plonk_comm* c, const uint8_t* h_send, size_t bytes_per_
 }
 
 // The gather of a step's proofs without the host round trip of plonk_gather_results (D -> H -> D -> all-gather -> D -> H):
-// every prover of this rank packs its resident batch — records of 768 bytes, or 480 compressed — and its status bytes
+// every prover of this rank packs its resident batch — plain or compressed records (prover.h) — and its status bytes
 // straight into the send buffer on its own stream, the communicator's stream waits for those streams' events, ONE
 // ncclAllGather moves proofs and status bytes of all ranks over xGMI, and one copy brings them to the host.
 // h_recv[r] = [n_provers * batch records | n_provers * batch status bytes, padded to 16] of rank r.
@@ -336,7 +336,7 @@ int plonk_gather_proofs_device(plonk_comm* c, plonk_prover* const* provers, size
     PLONK_REQUIRE(c && provers && n_provers && batch && h_recv, PLONK_ERR_ARG, "bad argument");
     PLONK_COMM_LIVE(c);
     PLONK_ENTER(c->ctx);
-    const size_t rec = compressed ? 480 : 768;
+    const size_t rec = prover_record_bytes(compressed);
     const size_t n = n_provers * batch;
     const size_t per_rank = n * rec + ((n + 15) & ~(size_t)15);
     const size_t total = per_rank * (size_t)c->world;

@@ -48,6 +48,17 @@ template <class P> PLONK_HD bool fp_eq(const Fp<P>& a, const Fp<P>& b) {
     for (int i = 0; i < 8; i++) o |= a.v[i] ^ b.v[i];
     return o == 0;
 }
+// the eight little-endian words are a canonical value: v < m
+template <class P> PLONK_HD bool fp_below_modulus(const uint32_t v[8]) {
+    bool lt = false, eq = true;
+#pragma unroll
+    for (int k = 7; k >= 0; k--)
+        if (eq && v[k] != P::mod(k)) {
+            lt = v[k] < P::mod(k);
+            eq = false;
+        }
+    return lt;
+}
 
 // 32-bit add/sub with carry.  clang lowers the builtins to v_add_co / v_addc_co chains (one VALU op per
 // limb); the portable u64 form compiles to v_lshl_add_u64 plus register-pair moves, ~3x the instructions.

@@ -38,6 +38,12 @@ PLONK_HD G1Xyzz g1_xyzz_from_affine(const G1Affine& p) {
     r.x = p.x; r.y = p.y; r.zz = fp_one<FqParams>(); r.zzz = fp_one<FqParams>();
     return r;
 }
+// y^2 == x^3 + 3 (Montgomery coordinates); the cofactor is 1, so on the curve is in the group
+PLONK_HD bool g1_affine_on_curve(const Fq& x, const Fq& y) {
+    Fq three = fp_zero<FqParams>();
+    three.v[0] = 3;
+    return fp_eq(fp_sqr(y), fp_add(fp_mul(fp_sqr(x), x), fp_to_mont(three)));
+}
 PLONK_HD G1Affine g1_affine_neg(const G1Affine& p) {
     G1Affine r;
     r.x = p.x; r.y = fp_neg(p.y);

@@ -39,6 +39,27 @@ template <class T> static inline bool plonk_host_malloc(T** p, size_t bytes) {
     return false;
 }
 
+// an object's own device buffers (prover, verifier): allocation that reports, and the one way to release — every pointer
+// that is set is freed and nulled
+static inline int dev_alloc(void** p, size_t bytes) {
+    if (plonk_dev_malloc(p, bytes ? bytes : 32)) return PLONK_OK;
+    plonk_set_error("hipMalloc(%zu) failed", bytes);
+    return PLONK_ERR_NOMEM;
+}
+static inline void dev_free_all(std::initializer_list<void**> ptrs) {
+    for (void** q : ptrs) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+}
+
+static inline Fr host_fr_u64(uint64_t x) {  // a small integer in Montgomery form
+    Fr a = fp_zero<FrParams>();
+    a.v[0] = (uint32_t)x;
+    a.v[1] = (uint32_t)(x >> 32);
+    return fp_to_mont(a);
+}
+
 #define PLONK_REQUIRE(cond, code, ...)    \
     do {                                  \
         if (!(cond)) {                    \
@@ -217,3 +238,4 @@ int msm_run_device(plonk_ctx*, plonk_srs*, const Fr* d_scalars, size_t n, size_t
 struct plonk_prover;
 int prover_pack_device(plonk_prover* p, size_t B, int compressed, uint8_t* d_proofs, uint8_t* d_status, hipEvent_t done);
 plonk_ctx* prover_ctx(plonk_prover* p);
+size_t prover_record_bytes(int compressed);  // bytes of one packed proof record (prover.h)

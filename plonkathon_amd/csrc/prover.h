@@ -1,0 +1,90 @@
+// prover.h — what prover.hip and verifier.hip share (internal): the per-proof state, the resident batch, the status bits and the
+// layout of a proof record.
+#pragma once
+#include "plonk_internal.h"
+#include "transcript_device.h"
+
+#define NEVAL 7  // a, b, c, s1, s2, z_shifted, PI(zeta)
+
+struct ProofState {
+    Fr beta, gamma, alpha, fft_cofactor, zeta, v;
+    Fr evals[NEVAL];
+    MerlinState transcript;
+    uint32_t error;  // 1: a commitment was the identity (the reference's append_point(None) raises)
+    uint32_t pad_[3];
+};
+
+// the prover's status byte (pack_status_kernel; 0 = the proof is good)
+#define PROVER_ST_IDENTITY 1u   // a commitment was the identity
+#define PROVER_ST_Z_OPEN 2u     // Z does not close to 1: the witness breaks the copy constraints (prover.py:132)
+#define PROVER_ST_GATE 4u       // a gate constraint fails on some row (prover.py:108-116)
+#define PROVER_ST_BAD_INPUT 8u  // an asynchronously uploaded value was not below r
+
+// A proof record: nine commitments a_1, b_1, c_1, z_1, t_lo_1, t_mid_1, t_hi_1, W_z_1, W_zw_1, then the six evaluations a, b, c,
+// s1, s2, z_shifted.  Plain: x || y and the evaluations as canonical little-endian words.  Compressed (g1_codec.h): 32 bytes per
+// point, the evaluations big-endian.
+#define PROOF_POINTS 9
+#define PROOF_EVALS 6
+#define PROOF_BYTES (64 * PROOF_POINTS + 32 * PROOF_EVALS)
+#define PROOF_BYTES_COMPRESSED (32 * PROOF_POINTS + 32 * PROOF_EVALS)
+#define PROOF_COMPRESSED_EVALS (32 * PROOF_POINTS)  // byte offset of the scalars in a compressed record
+constexpr unsigned proof_point_word(unsigned k, unsigned h) { return 16 * k + 8 * h; }  // coordinate h (x, y) of point k, plain record
+constexpr unsigned proof_eval_word(unsigned e) { return 16 * PROOF_POINTS + 8 * e; }
+constexpr size_t proof_bytes(bool compressed) { return compressed ? PROOF_BYTES_COMPRESSED : PROOF_BYTES; }
+
+#define PI_SPARSE_MAX 8
+enum { FX_QM = 0, FX_QL, FX_QR, FX_QO, FX_QC, FX_S1, FX_S2, FX_S3, FX_COUNT };
+#define QCOSETS 3  // cosets of size n the lock-step prover evaluates the quotient on (deg t < 3n)
+
+struct plonk_prover {
+    plonk_ctx* ctx;
+    plonk_srs* srs;
+    unsigned log_n;
+    size_t n, n_public;
+    Fr g;                // fixed coset offset (Montgomery)
+    Fr w, n_inv, half;   // the n-th root of unity, 1 / n, 1 / 2
+    // The quotient has degree < 3n, so THREE cosets of the n-th roots of unity determine it: x = g mu^r w^j, r < 3 (mu = the
+    // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.
+    Fr* fixed_lag;       // [8][n]   Lagrange values
+    Fr* fixed_coef;      // [8][n]   coefficient forms
+    Fr* fixed_big;       // [8][3][n]  the circuit polynomials on the three cosets
+    Fr* l0_big;          // [3][n]
+    Fr* x_big;           // [3][n]   the points g mu^r w^j
+    Fr* g_pow;           // [3][n]   (g mu^r)^i: the load-side scaling of the size-n transform that evaluates on coset r
+    Fr* ginv_pow;        // [3][n]   (g mu^r)^-i / 2n: the store-side scaling of the inverse transform of coset r (its 1/n folded in)
+    const Fr* roots;     // [n]      w^i (owned by ctx)
+    Fr zh_inv[QCOSETS];  // 1 / (g^n * i^r - 1): Z_H is constant on a coset
+    Fr comb_i, comb_g1, comb_g2;  // quotient_combine_kernel's constants: i = mu^n, 1 / g^n, 1 / g^2n
+    // Public inputs are the only non-zero entries of the PI column (prover.py:57-62): with few of them PI's
+    // coefficient and coset forms are cheaper from the Lagrange basis directly than through two transforms.
+    bool sparse_pi;      // n_public <= PI_SPARSE_MAX
+    Fr* li_big;          // [n_public][4n]  L_i on the coset: (w^i / n) Z_H(x_k) / (x_k - w^i)
+    const Fr* roots_inv; // [n]             w^-i (owned by ctx)
+    Fr* pub;             // [B][n_public]   public inputs of the resident batch (Montgomery)
+    // per-batch buffers (capacity cap_b proofs)
+    size_t cap_b;
+    Fr *wit_lag;   // [4][B][n]  A, B, C, PI   Lagrange
+    Fr *z_lag;     // [B][n]
+    Fr *coef;      // [5][B][n]  Ac, Bc, Cc, PIc, Zc   (coefficient forms; Z last so rounds 1 and 2 fill it in order)
+    Fr *big;       // [5][B][3][n] A, B, C, PI, Z on the three cosets
+    Fr *quot;      // [B][4n]    quotient evaluations on the three cosets, then its 3n coefficients (in place; the last n unused)
+    Fr *num;       // [B][n]     round 2: the grand product's numerator factors (the denominators' go to wz); round 5: W_z's numerator
+    uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
+    Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
+    struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
+    // wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device
+    uint32_t* cell_index;      // [3][n]  variable index of each wire cell; n_vars = empty cell / padding row
+    uint32_t* pub_index;       // [n_public]
+    size_t n_vars;
+    Fr* vars;                  // [B][n_vars] values of the resident batch (Montgomery)
+    size_t vars_cap;           // elements
+    plonk_srs* lag_srs;        // Lagrange-basis view of srs (PLONK_PROVER_LAGRANGE_COMMITS), owned by srs
+    size_t resident_b;         // batch size of the witnesses currently resident (run / download must match it)
+    unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
+    hipEvent_t ev_copied, ev_vars_read;  // async upload: the copy stream's H2D is done / the gather kernels have read `vars`
+    bool vars_read_pending;
+    Fq *commit_xy; // [9][B] x||y canonical
+    uint8_t* commit_flags;  // [9][B]
+    ProofState* state;      // [B]
+    ChallengeConsts chal;   // for the challenge reduction in transcript_kernel
+};

@@ -1,39 +1,26 @@
-// verifier.h — the batch verifier (plonk_verifier_*, plonk_g1_mul_many): N proofs of one circuit, one pairing check.
+// verifier.hip — the batch verifier (plonk_verifier_*, plonk_g1_mul_many): N proofs of one circuit, one pairing check.
 //
 // Reference behaviour replaced: verify_proof of TESTING_verifier_DO_NOT_OPEN.py:39-163 (challenges :266-277) for a batch.  Every
 // proof's check is e(L_i, [x]_2) == e(R_i, [1]_2) with L_i, R_i in G1, so with random 128-bit weights rho_i the batch is accepted
 // iff e(sum rho_i L_i, [x]_2) == e(sum rho_i R_i, [1]_2): the device returns the two sums, the pairing stays on the host
-// (plonk_pairing_check).  Included from prover.hip, which owns the record layout, the device transcript (tc_*) and the resident
-// batch.  Three steps per loaded batch:
+// (plonk_pairing_check).  The record layout and the resident batch are prover.h's, the device transcript transcript_device.h's.
+// Three steps per loaded batch:
 //   verify_scalars_kernel   32 lanes per proof: well-formedness, transcript replay, the weighted scalars of the proof's terms
 //   g1_mul_many_kernel      one lane per (proof, term): k * P by double-and-add on the complete formulas of g1.h
 //   verify_fold_proof_kernel / verify_fold_kernel   L_i, R_i per proof (kept), then the sum over any range [lo, hi) + the nine
 //                           fixed-point products (their scalars are summed over the range in Fr first) -> two affine points
-#pragma once
+#include <string.h>
+
+#include "plonk_internal.h"
+#include "transcript.h"
+#include "transcript_device.h"
+#include "prover.h"
 
 #define VF_OWN 11    // a_1, b_1, c_1, z_1, t_lo_1, t_mid_1, t_hi_1, W_z_1, W_zw_1 in R_i;  W_z_1, W_zw_1 in L_i
 #define VF_FIXED 9   // Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1
 #define VF_MALFORMED 1u
 #define VF_OFF_CURVE 2u
 #define VF_IDENTITY 4u
-
-template <class P> PLONK_HD bool vf_below_modulus(const uint32_t v[8]) {
-    bool lt = false, eq = true;
-#pragma unroll
-    for (int k = 7; k >= 0; k--)
-        if (eq && v[k] != P::mod(k)) {
-            lt = v[k] < P::mod(k);
-            eq = false;
-        }
-    return lt;
-}
-
-// y^2 == x^3 + 3 (Montgomery coordinates)
-PLONK_HD bool vf_on_curve(const Fq& x, const Fq& y) {
-    Fq three = fp_zero<FqParams>();
-    three.v[0] = 3;
-    return fp_eq(fp_sqr(y), fp_add(fp_mul(fp_sqr(x), x), fp_to_mont(three)));
-}
 
 // k * p for a canonical k < 2^254 and an affine p: left-to-right double-and-add on the complete formulas of g1.h.  The scalar
 // is shifted out of its top bit, so its words keep constant indices; the fences keep the scheduler from interleaving the
@@ -87,7 +74,7 @@ PLONK_DEV void vf_store_xyzz(G1Xyzz* p, const G1Xyzz& r) {
     fp_store(&p->zzz, r.zzz);
 }
 
-// Per proof: 768-byte record + public inputs -> status byte, the eleven points in Montgomery form, their weighted scalars
+// Per proof: plain record (prover.h) + public inputs -> status byte, the eleven points in Montgomery form, their weighted scalars
 // (canonical: g1_mul_many_kernel reads bits) and the nine weighted fixed-point scalars (Montgomery: verify_fold_kernel sums them).
 // Lane layout of transcript_kernel: 32 lanes per proof, two proofs per workgroup, barriers uniform — a malformed proof replays the
 // transcript over its bytes as they are and its results are dropped (weight zero: identity points, zero scalars).
@@ -108,7 +95,7 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
     size_t b = (size_t)blockIdx.x * 2 + grp;
     const bool live = b < B;
     if (!live) b = B - 1;  // shadow the last proof so the barriers stay uniform; nothing is stored
-    const uint32_t* rec = reinterpret_cast<const uint32_t*>(proofs + b * 768);
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(proofs + b * PROOF_BYTES);
     if (lane == 0) shared[grp].status = 0;
     __syncthreads();
 
@@ -120,78 +107,49 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
         Fq x, y;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            x.v[i] = rec[16 * k + i];
-            y.v[i] = rec[16 * k + 8 + i];
+            x.v[i] = rec[proof_point_word(k, 0) + i];
+            y.v[i] = rec[proof_point_word(k, 1) + i];
         }
-        if (!vf_below_modulus<FqParams>(x.v) || !vf_below_modulus<FqParams>(y.v)) bad = VF_MALFORMED;
+        if (!fp_below_modulus<FqParams>(x.v) || !fp_below_modulus<FqParams>(y.v)) bad = VF_MALFORMED;
         else if (fp_is_zero(x) && fp_is_zero(y)) bad = VF_IDENTITY;  // the reference's transcript refuses None (transcript.py:62-67)
         else {
             P.x = fp_to_mont(x);
             P.y = fp_to_mont(y);
-            if (!vf_on_curve(P.x, P.y)) bad = VF_OFF_CURVE;  // cofactor 1: on the curve is in the group
+            if (!g1_affine_on_curve(P.x, P.y)) bad = VF_OFF_CURVE;  // cofactor 1: on the curve is in the group
         }
-    } else if (lane < VF_OWN + 6) {
+    } else if (lane < VF_OWN + PROOF_EVALS) {
         uint32_t e[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) e[i] = rec[144 + 8 * (lane - VF_OWN) + i];
-        if (!vf_below_modulus<FrParams>(e)) bad = VF_MALFORMED;
+        for (int i = 0; i < 8; i++) e[i] = rec[proof_eval_word(lane - VF_OWN) + i];
+        if (!fp_below_modulus<FrParams>(e)) bad = VF_MALFORMED;
     }
     if (bad) atomicOr(&shared[grp].status, bad);
     __syncthreads();
     const uint32_t st = shared[grp].status;
 
     // ---- transcript replay (TESTING_verifier:266-277)
-    TcState t;
-    t.w = lane < 25 ? init[0].st[lane] : 0;
-    t.pos = init[0].pos;
-    t.pos_begin = init[0].pos_begin;
-    auto stage_points = [&](unsigned first, unsigned count) {  // big-endian x, y of `count` commitments to sh.msg
+    TcState t = tc_load(init[0], lane);
+    Fr beta, gamma, alpha, zeta, v, u, unused;
+    // staging: `count` 32-byte values from rec[word], big-endian, to sh.msg
+    const auto round = [&](int r, unsigned word, unsigned count, Fr& c0, Fr& c1) PLONK_LAMBDA_INLINE {
         __syncthreads();  // earlier readers of sh.msg are done
-        if (lane < 2 * count) {
-            uint32_t v[8];
+        if (lane < count) {
+            uint32_t x[8];
 #pragma unroll
-            for (int i = 0; i < 8; i++) v[i] = rec[16 * first + 8 * lane + i];
-            limbs_to_be32(v, sh.msg + 32 * lane);
+            for (int i = 0; i < 8; i++) x[i] = rec[word + 8 * lane + i];
+            limbs_to_be32(x, sh.msg + 32 * lane);
         }
         __syncthreads();
+        tc_round(t, sh, lane, cc, r, c0, c1);
     };
-    auto absorb_point = [&](int k, const char* label, unsigned llen) {
-        tc_append_message(t, sh, lane, label, llen, sh.msg + 64 * k, 32);
-        tc_append_message(t, sh, lane, label, llen, sh.msg + 64 * k + 32, 32);
-    };
-    stage_points(0, 3);
-    absorb_point(0, "a_1", 3);
-    absorb_point(1, "b_1", 3);
-    absorb_point(2, "c_1", 3);
-    const Fr beta = tc_draw(t, sh, lane, cc, "beta", 4);
-    const Fr gamma = tc_draw(t, sh, lane, cc, "gamma", 5);
-    stage_points(3, 1);
-    absorb_point(0, "z_1", 3);
-    const Fr alpha = tc_draw(t, sh, lane, cc, "alpha", 5);
-    (void)tc_draw(t, sh, lane, cc, "fft_cofactor", 12);
-    stage_points(4, 3);
-    absorb_point(0, "t_lo_1", 6);
-    absorb_point(1, "t_mid_1", 7);
-    absorb_point(2, "t_hi_1", 6);
-    const Fr zeta = tc_draw(t, sh, lane, cc, "zeta", 4);
-    stage_points(9, 3);  // the six evaluations follow the nine points in the record, 32 bytes each: coordinates 18..23
-    tc_append_message(t, sh, lane, "a_eval", 6, sh.msg, 32);
-    tc_append_message(t, sh, lane, "b_eval", 6, sh.msg + 32, 32);
-    tc_append_message(t, sh, lane, "c_eval", 6, sh.msg + 64, 32);
-    tc_append_message(t, sh, lane, "s1_eval", 7, sh.msg + 96, 32);
-    tc_append_message(t, sh, lane, "s2_eval", 7, sh.msg + 128, 32);
-    tc_append_message(t, sh, lane, "z_shifted_eval", 14, sh.msg + 160, 32);
-    const Fr v = tc_draw(t, sh, lane, cc, "v", 1);
-    stage_points(7, 2);
-    absorb_point(0, "W_z_1", 5);
-    absorb_point(1, "W_zw_1", 6);
-    const Fr u = tc_draw(t, sh, lane, cc, "u", 1);
+    round(1, proof_point_word(0, 0), 6, beta, gamma);
+    round(2, proof_point_word(3, 0), 2, alpha, unused);  // fft_cofactor is drawn and dropped
+    round(3, proof_point_word(4, 0), 6, zeta, unused);
+    round(4, proof_eval_word(0), PROOF_EVALS, v, unused);
+    round(5, proof_point_word(7, 0), 4, u, unused);
 
     // ---- the weight: a clone of the seeded transcript, the proof's index, 16 challenge bytes read little-endian
-    TcState tr;
-    tr.w = lane < 25 ? init[1].st[lane] : 0;
-    tr.pos = init[1].pos;
-    tr.pos_begin = init[1].pos_begin;
+    TcState tr = tc_load(init[1], lane);
     __syncthreads();
     if (lane < 8) sh.msg[lane] = (uint8_t)((uint64_t)b >> (8 * lane));
     __syncthreads();
@@ -223,12 +181,12 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
     for (int i = 0; i < 4; i++)
         rho.v[i] = (uint32_t)sh.msg[4 * i] | ((uint32_t)sh.msg[4 * i + 1] << 8) | ((uint32_t)sh.msg[4 * i + 2] << 16) | ((uint32_t)sh.msg[4 * i + 3] << 24);
     rho = fp_to_mont(rho);
-    Fr ev[6];
+    Fr ev[PROOF_EVALS];
 #pragma unroll
-    for (int e = 0; e < 6; e++) {
+    for (int e = 0; e < PROOF_EVALS; e++) {
         Fr x;
 #pragma unroll
-        for (int i = 0; i < 8; i++) x.v[i] = rec[144 + 8 * e + i];
+        for (int i = 0; i < 8; i++) x.v[i] = rec[proof_eval_word(e) + i];
         ev[e] = fp_to_mont(x);
     }
     const Fr a = ev[0], bb = ev[1], c = ev[2], s1 = ev[3], s2 = ev[4], zw = ev[5];
@@ -364,7 +322,7 @@ __global__ void g1_mul_many_in_kernel(Fq* xy, const Fr* scalars, size_t count, u
     if (j >= count) return;
     const Fq x = fp_load(xy + 2 * j), y = fp_load(xy + 2 * j + 1);
     const Fr k = fp_load(scalars + j);
-    if (!vf_below_modulus<FqParams>(x.v) || !vf_below_modulus<FqParams>(y.v) || !vf_below_modulus<FrParams>(k.v)) {
+    if (!fp_below_modulus<FqParams>(x.v) || !fp_below_modulus<FqParams>(y.v) || !fp_below_modulus<FrParams>(k.v)) {
         atomicOr(bad, 1u);
         fp_store(xy + 2 * j, fp_zero<FqParams>());
         fp_store(xy + 2 * j + 1, fp_zero<FqParams>());
@@ -372,7 +330,7 @@ __global__ void g1_mul_many_in_kernel(Fq* xy, const Fr* scalars, size_t count, u
     }
     if (fp_is_zero(x) && fp_is_zero(y)) return;
     const Fq xm = fp_to_mont(x), ym = fp_to_mont(y);
-    if (!vf_on_curve(xm, ym)) atomicOr(bad, 2u);
+    if (!g1_affine_on_curve(xm, ym)) atomicOr(bad, 2u);
     fp_store(xy + 2 * j, xm);
     fp_store(xy + 2 * j + 1, ym);
 }
@@ -398,7 +356,7 @@ struct plonk_verifier {
     MerlinState* d_init;
     G1Affine* d_bases;       // [9] Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1 (Montgomery)
     size_t cap, batch;       // allocated / loaded proofs
-    uint8_t* d_proofs;       // [B][768]
+    uint8_t* d_proofs;       // [B][PROOF_BYTES]
     Fr* d_pub;               // [B][n_public] Montgomery
     Fr* d_inv_tmp;           // [B][max(n_public, 1)]
     G1Affine* d_pts;         // [B][11]
@@ -412,13 +370,8 @@ struct plonk_verifier {
 };
 
 static void verifier_free_batch(plonk_verifier* v) {
-    void* bufs[] = {v->d_proofs, v->d_pub, v->d_inv_tmp, v->d_pts, v->d_own, v->d_fixed, v->d_prod, v->d_lr, v->d_status};
-    for (void* q : bufs)
-        if (q) hipFree(q);
-    v->d_proofs = v->d_status = nullptr;
-    v->d_pub = v->d_inv_tmp = v->d_own = v->d_fixed = nullptr;
-    v->d_pts = nullptr;
-    v->d_prod = v->d_lr = nullptr;
+    dev_free_all({(void**)&v->d_proofs, (void**)&v->d_pub, (void**)&v->d_inv_tmp, (void**)&v->d_pts, (void**)&v->d_own, (void**)&v->d_fixed,
+                  (void**)&v->d_prod, (void**)&v->d_lr, (void**)&v->d_status});
     v->cap = v->batch = 0;
 }
 
@@ -427,7 +380,7 @@ static int verifier_ensure(plonk_verifier* v, size_t B) {
     PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));
     verifier_free_batch(v);
     const size_t m = v->n_public ? v->n_public : 1;
-    PLONK_TRY(dev_alloc((void**)&v->d_proofs, B * 768));
+    PLONK_TRY(dev_alloc((void**)&v->d_proofs, B * PROOF_BYTES));
     PLONK_TRY(dev_alloc((void**)&v->d_pub, B * m * sizeof(Fr)));
     PLONK_TRY(dev_alloc((void**)&v->d_inv_tmp, B * m * sizeof(Fr)));
     PLONK_TRY(dev_alloc((void**)&v->d_pts, B * VF_OWN * sizeof(G1Affine)));
@@ -467,14 +420,7 @@ static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned log_n, cons
     v->dom.w = host_root_of_unity(log_n, false);
     v->dom.w_inv = host_root_of_unity(log_n, true);
     v->dom.n_inv = fp_inv(host_fr_u64((uint64_t)1 << log_n));
-    {   // transcript_kernel's challenge constants (prover_init)
-        Fr t = fp_zero<FrParams>();
-        t.v[4] = 1;
-        t = fp_to_mont(t);
-        const Fr two256 = fp_mul(t, t);
-        for (int i = 0; i < 8; i++) v->chal.c[0].v[i] = FrParams::r2(i);
-        for (int j = 1; j < 8; j++) v->chal.c[j] = fp_mul(v->chal.c[j - 1], two256);
-    }
+    v->chal = challenge_consts();
     merlin_init(v->h_init[0], (const uint8_t*)"plonk", 5);
     v->h_init[1] = v->h_init[0];
     G1Affine bases[VF_FIXED];
@@ -486,7 +432,7 @@ static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned log_n, cons
         memcpy(y.v, q + 32, 32);
         bases[k].x = fp_to_mont(x);
         bases[k].y = fp_to_mont(y);
-        PLONK_REQUIRE(g1_affine_is_identity(bases[k]) || vf_on_curve(bases[k].x, bases[k].y), PLONK_ERR_ARG, "verification key point %d is not on the curve", k);
+        PLONK_REQUIRE(g1_affine_is_identity(bases[k]) || g1_affine_on_curve(bases[k].x, bases[k].y), PLONK_ERR_ARG, "verification key point %d is not on the curve", k);
     }
     bases[8].x = fp_one<FqParams>();  // G1 = (1, 2)
     bases[8].y = fp_dbl(bases[8].x);
@@ -523,21 +469,19 @@ int plonk_verifier_destroy(plonk_verifier* v) {
         hipStreamSynchronize(v->ctx->stream);
     }
     verifier_free_batch(v);
-    void* bufs[] = {v->d_init, v->d_bases, v->d_out};
-    for (void* q : bufs)
-        if (q) hipFree(q);
+    dev_free_all({(void**)&v->d_init, (void**)&v->d_bases, (void**)&v->d_out});
     if (v->ev) hipEventDestroy(v->ev);
     delete v;
     return PLONK_OK;
 }
 
-int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs768, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]) {
-    PLONK_REQUIRE(v && proofs768 && batch && seed && (public_le32 || !v->n_public), PLONK_ERR_ARG, "bad argument");
+int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && proofs && batch && seed && (public_le32 || !v->n_public), PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(v->ctx);
     v->batch = 0;  // until the new batch is in place
     PLONK_TRY(verifier_ensure(v, batch));
     if (v->n_public) PLONK_TRY(plonk_fr_upload(v->ctx, v->d_pub, public_le32, batch * v->n_public));  // a value not below r: PLONK_ERR_ARG
-    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_proofs, proofs768, batch * 768, hipMemcpyHostToDevice, v->ctx->stream));
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_proofs, proofs, batch * PROOF_BYTES, hipMemcpyHostToDevice, v->ctx->stream));
     return verifier_run(v, batch, seed);
 }
 
@@ -590,14 +534,13 @@ int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_s
     PLONK_ENTER(ctx);
     if (!count) return PLONK_OK;
     void* buf;
-    PLONK_TRY(ctx_scratch(ctx, 3, count * (64 + 32 + 128 + 64 + 1) + 64, &buf));
-    uint8_t* base = (uint8_t*)buf;
-    Fq* d_xy = (Fq*)base;
-    Fr* d_k = (Fr*)(base + count * 64);
-    G1Xyzz* d_prod = (G1Xyzz*)(base + count * 96);
-    Fq* d_out = (Fq*)(base + count * 224);
-    uint32_t* d_bad = (uint32_t*)(base + count * 288);
-    uint8_t* d_flags = base + count * 288 + 16;
+    PLONK_TRY(ctx_scratch(ctx, 3, count * (2 * sizeof(Fq) + sizeof(Fr) + sizeof(G1Xyzz) + 2 * sizeof(Fq) + 1) + 64, &buf));
+    Fq* d_xy = (Fq*)buf;
+    Fr* d_k = (Fr*)(d_xy + 2 * count);
+    G1Xyzz* d_prod = (G1Xyzz*)(d_k + count);
+    Fq* d_out = (Fq*)(d_prod + count);
+    uint32_t* d_bad = (uint32_t*)(d_out + 2 * count);
+    uint8_t* d_flags = (uint8_t*)(d_bad + 4);
     hipStream_t s = ctx->stream;
     const dim3 grid((unsigned)((count + 63) / 64));
     PLONK_CHECK_HIP(hipMemcpyAsync(d_xy, h_xy_le, count * 64, hipMemcpyHostToDevice, s));
