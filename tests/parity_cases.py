@@ -1284,3 +1284,427 @@ def proofs_verify(setup, lines, group_order, start, public):
     bad = dict(proof)
     bad["b_eval"] = (bad["b_eval"] + 1) % R_MOD
     assert not ovk.verify_proof(group_order, bad, pub)
+
+
+# ------------------------------------------------------------------------------------------ multi-rank NTT passes on one device
+def random_canonical_bytes(seed, n):
+    """n canonical elements (< 2^253 < r) as 32-byte little-endian words, from a seeded numpy generator."""
+    import numpy as np
+
+    a = np.random.default_rng(seed).integers(0, 256, size=(n, 32), dtype=np.uint8)
+    a[:, 31] &= 0x1F
+    return a.tobytes()
+
+
+def dist_split(log_n):
+    """(log R1, log R2) of the library's default two-pass split of 2^log_n: the layouts of the distributed transform follow it."""
+    import ctypes
+
+    from plonkathon_amd import _lib
+
+    r1 = ctypes.c_uint(0)
+    _lib.check(_lib.lib().plonk_ntt_get_split(None, log_n, ctypes.byref(r1)))
+    return r1.value, log_n - r1.value
+
+
+def dist_max_log_world(log_n):
+    """The most ranks ntt_dist_plan (csrc/ntt.hip) admits: 2^5 columns and 2^5 rows per rank at the least."""
+    return min(dist_split(log_n)) - 5
+
+
+def _dist_input(log_n, data, seed):
+    """The (N, 32) uint8 input: random canonical elements, or a pattern that drives the limb-form kernels' range bounds."""
+    import numpy as np
+
+    n = 1 << log_n
+    if data == "random":
+        return np.frombuffer(random_canonical_bytes(seed, n), dtype=np.uint8).reshape(n, 32)
+    top = np.frombuffer((R_MOD - 1).to_bytes(32, "little"), dtype=np.uint8)
+    full = np.zeros((n, 32), dtype=np.uint8)
+    if data == "max":             # every element r - 1
+        full[:] = top
+    elif data == "last":          # a lone r - 1 at the last index
+        full[n - 1] = top
+    elif data == "alt":           # 1, r - 1, 1, r - 1, ..
+        full[0::2, 0] = 1
+        full[1::2] = top
+    else:
+        assert data == "zero", data
+    return full
+
+
+def dist_ntt_ranks_on_one_device(log_n, log_ws, inverse, data="random", seed=0):
+    """The local passes of the distributed four-step transform (plonk_fr_ntt_dist_columns / _rows) for EVERY rank of W = 2^log_w,
+    run in turn on this one device, with the all-to-all between them done as a block transpose by device copies: the
+    rank-dependent twiddle column, the chunked gather of the row pass over [source rank][R1/W][R2/W] and the inverse's 1/N,
+    exact against the C oracle's transform of the whole vector.  Rank g's input is its columns [R1][R2/W]; rank h's output holds
+    frequency k1 + R1 k2 at [k2][k1 - h R1/W].  The column passes run in the order W - 1 .. 0 and the row passes in another, so a
+    rank that picked up another rank's state from the context (tables, scratch) would show."""
+    import numpy as np
+
+    from oracle import c_oracle
+    from plonkathon_amd import get_context
+    from plonkathon_amd._lib import check
+
+    ctx = get_context()
+    L, n = ctx.L, 1 << log_n
+    log_r1, log_r2 = dist_split(log_n)
+    R1, R2 = 1 << log_r1, 1 << log_r2
+    full = _dist_input(log_n, data, seed or 5000 + 2 * log_n + int(inverse))
+    want = np.frombuffer(c_oracle.fr_ntt_bytes(full.tobytes(), inverse), dtype=np.uint8)
+    print("distributed NTT 2^%d = 2^%d x 2^%d, log_w in %s, %s, %s" % (log_n, log_r1, log_r2, list(log_ws), "inverse" if inverse else "forward", data))
+    for log_w in log_ws:
+        W = 1 << log_w
+        local = n >> log_w   # elements per rank
+        blk = local >> log_w  # elements rank g sends to rank h: rows k1 = h R1/W .. of its columns
+        mine = full.reshape(R1, W, R2 // W, 32)
+        theirs = want.reshape(R2, W, R1 // W, 32)
+        cols = [None] * W
+        for g in reversed(range(W)):
+            d_in = ctx.upload_bytes(mine[:, g].tobytes())
+            cols[g] = ctx.alloc(local)
+            check(L.plonk_fr_ntt_dist_columns(ctx.handle, d_in.ptr, cols[g].ptr, log_n, log_w, g, int(inverse)))
+        # the exchange: block h of rank g's column output becomes block g of rank h's receive buffer.  Raw copies: the column output
+        # is an intermediate of packed residues below 2r, which the Montgomery conversion of plonk_fr_download must not touch
+        recv = [ctx.alloc(local) for _ in range(W)]
+        for g in range(W):
+            for h in range(W):
+                check(L.plonk_mem_d2d(ctx.handle, recv[h].at(g * blk), cols[g].at(h * blk), 32 * blk))
+        for h in [(W // 2 + i) % W for i in range(W)]:
+            out = ctx.alloc(local)
+            if data != "random":  # a pooled buffer may hold an earlier result: a pattern's output must come from this call
+                check(L.plonk_mem_h2d(ctx.handle, out.ptr, b"\xa5" * (32 * local), 32 * local))
+            check(L.plonk_fr_ntt_dist_rows(ctx.handle, recv[h].ptr, out.ptr, log_n, log_w, h, int(inverse)))
+            assert ctx.download_bytes(out) == theirs[:, h].tobytes(), (log_n, log_w, h, inverse, data)
+
+
+def dist_ntt_refusals():
+    """What the two local passes refuse, as return codes (nothing is launched): one rank count past the plan's maximum, a size
+    below 2^16, a rank outside the world, and a transform in place."""
+    from plonkathon_amd import _lib, get_context
+
+    ctx = get_context()
+    a, b = ctx.alloc(64), ctx.alloc(64)
+    for fn in (ctx.L.plonk_fr_ntt_dist_columns, ctx.L.plonk_fr_ntt_dist_rows):
+        for inverse in (0, 1):
+            for log_n in (16, 18, 22):
+                top = dist_max_log_world(log_n)
+                assert fn(ctx.handle, a.ptr, b.ptr, log_n, top + 1, 0, inverse) == _lib.PLONK_ERR_ARG, (log_n, top)
+                assert fn(ctx.handle, a.ptr, b.ptr, log_n, top, 1 << top, inverse) == _lib.PLONK_ERR_ARG, (log_n, "rank == W")
+            assert fn(ctx.handle, a.ptr, b.ptr, 15, 1, 0, inverse) == _lib.PLONK_ERR_ARG
+            assert fn(ctx.handle, a.ptr, b.ptr, 16, 1, 2, inverse) == _lib.PLONK_ERR_ARG
+            assert fn(ctx.handle, a.ptr, a.ptr, 16, 1, 0, inverse) == _lib.PLONK_ERR_ARG
+
+
+# ------------------------------------------------------------------------------------------ launch geometries of csrc/fr_ops.hip
+# The constants of csrc/fr_ops.hip the counts below are derived from: grid_for caps a launch at FR_GRID_CAP workgroups, the
+# streaming kernels run FR_BLOCK lanes per workgroup over one element each, batch inverse and powers FR_CHUNK_BLOCK lanes
+# over chunks of FR_INV_CHUNK / FR_POW_CHUNK elements.  If grid_for or a chunk size changes, change them here: the large counts
+# must keep taking each kernel's grid-stride loop into a second, partial iteration.
+FR_GRID_CAP, FR_BLOCK, FR_CHUNK_BLOCK, FR_INV_CHUNK, FR_POW_CHUNK = 2048, 256, 64, 8, 16
+FR_SMALL_COUNTS = (1, 7, 8, 9, 13, 517)  # ragged: below, at and above a chunk; a partial third workgroup of 256 lanes
+
+
+def fr_second_pass_count(block, chunk, extra):
+    """One full grid pass (every workgroup of the capped grid), then one more full workgroup and `extra` elements of the next."""
+    return FR_GRID_CAP * block * chunk + block * chunk + extra
+
+
+FR_STREAM_COUNT = fr_second_pass_count(FR_BLOCK, 1, 3)                       # pointwise, scalar op, lincomb, rotate, equal, upload
+FR_INV_COUNT = fr_second_pass_count(FR_CHUNK_BLOCK, FR_INV_CHUNK, 5)         # a last chunk of 5
+FR_POW_COUNT = fr_second_pass_count(FR_CHUNK_BLOCK, FR_POW_CHUNK, 3)         # a last chunk of 3
+assert (FR_STREAM_COUNT, FR_INV_COUNT, FR_POW_COUNT) == (524547, 1049093, 2098179)
+FR_OPS_PARTS = ("pointwise", "scalar", "lincomb", "rotate", "inverse", "powers", "equal", "upload", "barycentric")
+
+
+def _le(v):
+    return b"".join(x.to_bytes(32, "little") for x in v)
+
+
+def _un(raw):
+    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+def _edge_positions(count, chunk=1):
+    """Indices where a grid-stride kernel over `chunk`-element lanes can go wrong: both ends, the last partial workgroup, both
+    sides of the boundary between the first and the second grid pass, and the ends of a chunk."""
+    second = FR_GRID_CAP * (FR_BLOCK if chunk == 1 else FR_CHUNK_BLOCK) * chunk  # first index of the second grid pass
+    last_group = (count - 1) // FR_BLOCK * FR_BLOCK
+    pos = set(range(8)) | set(range(count - 8, count)) | {last_group, last_group + 1, second - 1, second, second + 1, second + FR_BLOCK}
+    return sorted(p for p in pos if 0 <= p < count)
+
+
+def fr_ops_launch_geometries(parts=FR_OPS_PARTS, large=True, bary_log_ns=(9, 10, 12, 13, 16)):
+    """The streaming kernels of csrc/fr_ops.hip through the C-ABI at the launch geometries the golden vectors never reach
+    (they are powers of two up to 2^11 / 2^13): the small ragged counts, and for each kernel the smallest count that takes its
+    grid-stride loop behind the 2048-workgroup cap into a second, partial iteration; in place wherever the ABI allows it;
+    0, 1, r - 1 and equal operands at the edges.  References are Python integers (at the large counts compared as bytes, and
+    where a per-element inversion would take seconds by the defining property q b = a instead).  barycentric: every block size
+    (64, 128, 256 lanes) and the multi-chunk loop, against Horner evaluation of the coefficients."""
+    import ctypes
+    import random
+
+    from oracle import c_oracle
+    from plonkathon_amd import _lib, get_context
+    from plonkathon_amd._lib import OP_ADD, OP_DIV, OP_MUL, OP_SUB, check
+
+    ctx = get_context()
+    L, H, m = ctx.L, ctx.handle, R_MOD
+    rng = random.Random(20261018)
+    le32 = lambda x: x.to_bytes(32, "little")
+
+    def rand_ints(seed, n):
+        return rand_vec(seed, n) if n <= 4096 else _un(random_canonical_bytes(seed, n))
+
+    def dup(buf):
+        c = ctx.alloc(buf.n)
+        check(L.plonk_mem_d2d(H, c.ptr, buf.ptr, 32 * buf.n))
+        return c
+
+    guard = b"\xa5" * (32 * 16)
+
+    def guarded(count):
+        """an output buffer with sixteen elements of a known pattern behind its end"""
+        buf = ctx.alloc(count + 16)
+        check(L.plonk_mem_h2d(H, buf.at(count), guard, len(guard)))
+        return buf
+
+    def result(buf, count):
+        behind = ctypes.create_string_buffer(len(guard))
+        check(L.plonk_mem_d2h(H, behind, buf.at(count), len(guard)))
+        assert behind.raw == guard, "a kernel wrote past the end of its output (count %d)" % count
+        return ctx.download_bytes(buf, count)
+
+    def counts_of(big):
+        return FR_SMALL_COUNTS + ((big,) if large else ())
+
+    py_op = {OP_ADD: lambda x, y: (x + y) % m, OP_SUB: lambda x, y: (x - y) % m, OP_MUL: lambda x, y: x * y % m,
+             OP_DIV: lambda x, y: x * ofield.inv(y) % m}
+
+    def operands(count, seed):
+        """a, b with 0, 1, r - 1 and equal values planted at the edge positions, in every pairing"""
+        a, b = rand_ints(seed, count), rand_ints(seed + 1, count)
+        pairs = [(0, 0), (0, None), (None, 0), (1, m - 1), (m - 1, m - 1), (m - 1, 1), (None, "same"), (1, 1), (m - 1, None), (None, m - 1)]
+        for k, p in enumerate(_edge_positions(count)):
+            x, y = pairs[k % len(pairs)]
+            if x is not None:
+                a[p] = x
+            if y is not None:
+                b[p] = a[p] if y == "same" else y
+        a[count - 1], b[count - 1] = m - 1, m - 1  # (r - 1) op (r - 1) at the very last index, whatever the cycle put there
+        if count > 1:
+            b[count - 2] = 0                      # ... and a zero divisor next to it
+        return a, b
+
+    if "pointwise" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            a, b = operands(count, 100 + count)
+            A, B = ctx.upload_bytes(_le(a)), ctx.upload_bytes(_le(b))
+            for op in (OP_ADD, OP_SUB, OP_MUL, OP_DIV):
+                out = guarded(count)
+                check(L.plonk_fr_pointwise(H, op, A.ptr, B.ptr, out.ptr, count))
+                got = result(out, count)
+                if op == OP_DIV and count > 4096:  # q = a / b  <=>  q b = a where b != 0 (b is invertible: q is unique); x / 0 == 0
+                    q = _un(got)
+                    assert all((qi * bi - ai) % m == 0 if bi else qi == 0 for qi, ai, bi in zip(q, a, b)), ("div", count)
+                    assert all(qi < m for qi in q)
+                else:
+                    assert got == _le([py_op[op](x, y) for x, y in zip(a, b)]), (op, count)
+                a2, b2 = dup(A), dup(B)
+                check(L.plonk_fr_pointwise(H, op, a2.ptr, B.ptr, a2.ptr, count))
+                assert ctx.download_bytes(a2) == got, (op, count, "out == a")
+                check(L.plonk_fr_pointwise(H, op, A.ptr, b2.ptr, b2.ptr, count))
+                assert ctx.download_bytes(b2) == got, (op, count, "out == b")
+            for op in (OP_MUL, OP_DIV):
+                a2 = dup(A)
+                check(L.plonk_fr_pointwise(H, op, a2.ptr, a2.ptr, a2.ptr, count))
+                assert ctx.download_bytes(a2) == _le([x * x % m if op == OP_MUL else int(x != 0) for x in a]), (op, count, "a == b == out")
+
+    if "scalar" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            a, _ = operands(count, 200 + count)
+            raw = _le(a)
+            A = ctx.upload_bytes(raw)
+            cache = {}
+            for op in (OP_ADD, OP_SUB, OP_MUL, OP_DIV):
+                for s in (0, 1, m - 1, rng.randrange(2, m - 1)):
+                    for first_only in (0, 1):
+                        if first_only:  # the MONOMIAL rule: the scalar meets the constant term alone
+                            want = le32(py_op[op](a[0], s)) + raw[32:]
+                        else:  # (x - s = x + (r - s) and x / s = x * s^-1: eleven vectors to form instead of sixteen)
+                            key = (OP_ADD, (m - s) % m) if op == OP_SUB else (OP_MUL, ofield.inv(s)) if op == OP_DIV else (op, s)
+                            if count <= 4096:
+                                key = (op, s)
+                            if key not in cache:
+                                cache[key] = _le([py_op[key[0]](x, key[1]) for x in a])
+                            want = cache[key]
+                        out = guarded(count)
+                        check(L.plonk_fr_scalar_op(H, op, A.ptr, le32(s), out.ptr, count, first_only))
+                        assert result(out, count) == want, (op, s, first_only, count)
+                        a2 = dup(A)
+                        check(L.plonk_fr_scalar_op(H, op, a2.ptr, le32(s), a2.ptr, count, first_only))
+                        assert ctx.download_bytes(a2) == want, (op, s, first_only, count, "in place")
+
+    if "lincomb" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            a, b = operands(count, 300 + count)
+            vecs = [a, b, rand_ints(302 + count, count)]
+            bufs = [ctx.upload_bytes(_le(v)) for v in vecs]
+            for n_terms in (1, 6, 20):
+                which = [k % 3 for k in range(n_terms)]  # repeated operands
+                scal = [rng.randrange(m) for _ in range(n_terms)]
+                if n_terms > 1:
+                    scal[1], scal[n_terms - 1] = 0, m - 1
+                const = rng.randrange(1, m)
+                if count <= 4096:
+                    want = [(const + sum(s * vecs[w][i] for s, w in zip(scal, which))) % m for i in range(count)]
+                else:  # the same sum with the scalars of a repeated operand added up first: three products per element, not twenty
+                    tot = [sum(s for s, w in zip(scal, which) if w == j) for j in range(3)]
+                    want = [(const + tot[0] * x + tot[1] * y + tot[2] * z) % m for x, y, z in zip(*vecs)]
+                want = _le(want)
+                sb = b"".join(le32(s) for s in scal)
+                ptrs = (ctypes.c_void_p * n_terms)(*[bufs[w].ptr.value for w in which])
+                out = guarded(count)
+                check(L.plonk_fr_lincomb(H, n_terms, ptrs, sb, le32(const), out.ptr, count))
+                assert result(out, count) == want, (n_terms, count)
+                io = dup(bufs[0])  # out is the operand of term 0 (and of every repeat of it)
+                ptrs = (ctypes.c_void_p * n_terms)(*[(io if w == 0 else bufs[w]).ptr.value for w in which])
+                check(L.plonk_fr_lincomb(H, n_terms, ptrs, sb, le32(const), io.ptr, count))
+                assert ctx.download_bytes(io) == want, (n_terms, count, "out is a term")
+
+    if "rotate" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            a = rand_ints(400 + count, count)
+            A = ctx.upload_bytes(_le(a))
+            for shift in sorted({0, 1 % count, count - 1, rng.randrange(count)}):
+                out = guarded(count)
+                check(L.plonk_fr_rotate(H, A.ptr, out.ptr, count, shift))
+                assert result(out, count) == _le(a[shift:] + a[:shift]), (count, shift)
+
+    if "inverse" in parts:
+        for count in counts_of(FR_INV_COUNT):
+            v = [x or 1 for x in rand_ints(500 + count, count)]
+            C = FR_INV_CHUNK
+            second = FR_GRID_CAP * FR_CHUNK_BLOCK * C  # first element of the second grid pass
+            last = (count - 1) // C * C                # first element of the last (ragged) chunk
+            zeros = {0, C - 1, count - 1, last} | set(range(2 * C, 3 * C)) | {4 * C, 5 * C - 1} | set(range(second + C, second + 2 * C)) | {second, second - 1}
+            for p in zeros:  # first / last of a chunk, whole chunks, the ragged chunk, the last index; the same behind the grid cap
+                if 0 <= p < count:
+                    v[p] = 0
+            v[min(1, count - 1)] = v[min(1, count - 1)] and m - 1
+            raw = _le(v)
+            A = ctx.upload_bytes(raw)
+            out = guarded(count)
+            check(L.plonk_fr_batch_inverse(H, A.ptr, out.ptr, count))
+            got = result(out, count)
+            inv = _un(got)
+            # the defining property: out in = 1 where in != 0 — unique, since in is invertible — and out = 0 where in = 0
+            assert all((y * x) % m == 1 and y < m if x else y == 0 for x, y in zip(v, inv)), count
+            if count <= 4096:
+                assert inv == [pow(x, -1, m) if x else 0 for x in v], count
+            assert ctx.download_bytes(A) == raw  # the input is left alone
+            check(L.plonk_fr_batch_inverse(H, A.ptr, A.ptr, count))
+            assert ctx.download_bytes(A) == got, (count, "in place")
+
+    if "powers" in parts:
+        def powers_want(first, base, count):
+            """first * base^k, k < count, as bytes: the iterated product, cut short where it is periodic from the start"""
+            if first == 0 or base == 0:
+                return le32(first) + bytes(32 * (count - 1))
+            if base == 1:
+                return le32(first) * count
+            if base == m - 1:
+                return ((le32(first) + le32(m - first)) * (count // 2 + 1))[:32 * count]
+            out, cur = [], first
+            for _ in range(count):
+                out.append(cur)
+                cur = cur * base % m
+            return _le(out)
+
+        for count in counts_of(FR_POW_COUNT):
+            for base in (rng.randrange(2, m - 1), 1, m - 1, 0):
+                for first in (rng.randrange(1, m), 0):
+                    want = powers_want(first, base, count)
+                    if count <= 4096:  # the short cuts above against the plain iterated product
+                        seq, cur = [], first
+                        for _ in range(count):
+                            seq.append(cur)
+                            cur = cur * base % m
+                        assert want == _le(seq)
+                    out = guarded(count)
+                    check(L.plonk_fr_powers(H, le32(first), le32(base), count, out.ptr))
+                    assert result(out, count) == want, (count, base, first)
+
+    if "equal" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            a = rand_ints(600 + count, count)
+            A = ctx.upload_bytes(_le(a))
+            eq = ctypes.c_int(-1)
+            twin = dup(A)
+            check(L.plonk_fr_equal(H, A.ptr, twin.ptr, count, ctypes.byref(eq)))
+            assert eq.value == 1, count
+            check(L.plonk_fr_equal(H, A.ptr, A.ptr, count, ctypes.byref(eq)))
+            assert eq.value == 1, count
+            for p in sorted({0, count - 1, FR_GRID_CAP * FR_BLOCK - 1, FR_GRID_CAP * FR_BLOCK} & set(range(count))):  # a single difference: first, last, both sides of the second grid pass's start
+                other = dup(A)
+                one = ctx.upload_bytes(le32((a[p] + 1) % m))
+                check(L.plonk_mem_d2d(H, other.at(p), one.ptr, 32))
+                eq = ctypes.c_int(-1)
+                check(L.plonk_fr_equal(H, A.ptr, other.ptr, count, ctypes.byref(eq)))
+                assert eq.value == 0, (count, p)
+                check(L.plonk_fr_equal(H, other.ptr, A.ptr, count, ctypes.byref(eq)))
+                assert eq.value == 0, (count, p)
+
+    if "upload" in parts:
+        for count in counts_of(FR_STREAM_COUNT):
+            raw = bytearray(random_canonical_bytes(700 + count, count))
+            second = FR_GRID_CAP * FR_BLOCK
+            hi = min(second + 1, count - 1)  # (large counts: an index only the second grid pass reaches)
+            lo = hi // 2
+            buf = ctx.alloc(count)
+            for bad, value in (((hi,), m), ((hi,), (1 << 256) - 1), ((lo, hi), m), ((hi, count - 1), m + 1)):
+                blob = bytearray(raw)
+                for p in bad:
+                    blob[32 * p:32 * p + 32] = le32(value)
+                assert L.plonk_fr_upload(H, buf.ptr, bytes(blob), count) == _lib.PLONK_ERR_ARG, (count, bad)
+                msg = L.plonk_last_error().decode()
+                assert "element %d is not" % bad[0] in msg, (count, bad, msg)  # the first offender is the one named
+            blob = bytearray(raw)
+            blob[32 * hi:32 * hi + 32] = le32(m - 1)  # the largest canonical value passes, and comes back
+            check(L.plonk_fr_upload(H, buf.ptr, bytes(blob), count))
+            assert ctx.download_bytes(buf) == bytes(blob)
+
+    if "barycentric" in parts:
+        for log_n in bary_log_ns:
+            n, K = 1 << log_n, 16
+            raws = [random_canonical_bytes(800 + 20 * log_n + k, n) for k in range(K)]
+            bufs = [ctx.upload_bytes(r) for r in raws]
+            xs = [rng.randrange(m) for _ in range(K)]
+
+            def horner(k, x):  # the value of polynomial k at x from its coefficients: no root of unity, no inversion
+                acc = 0
+                for c in reversed(_un(c_oracle.fr_ntt_bytes(raws[k], True))):
+                    acc = (acc * x + c) % m
+                return acc
+
+            want = [horner(k, xs[k]) for k in range(K)]
+            ptrs = (ctypes.c_void_p * K)(*[b.ptr.value for b in bufs])
+            out = ctypes.create_string_buffer(32 * K)
+            check(L.plonk_fr_barycentric_many(H, K, ptrs, log_n, b"".join(le32(x) for x in xs), out))
+            assert _un(out.raw) == want, ("many", log_n)
+            one = ctypes.create_string_buffer(32)
+            for k in (0, K - 1):
+                check(L.plonk_fr_barycentric(H, bufs[k].ptr, log_n, le32(xs[k]), one))
+                assert _un(one.raw) == [want[k]], ("single", log_n, k)
+            # ON the domain (x - w^i = 0 for one i: that term counts 0, as py_ecc's x / 0) at the edges of a lane's chunk of eight,
+            # and at 0: the oracle's own barycentric_eval
+            w = ofield.root_of_unity(n)
+            opoly = OPoly(_un(raws[0]), OBasis.LAGRANGE)
+            pts = [pow(w, k, m) for k in (0, 7, 8, n - 1)] + [0]
+            oracle_at = [opoly.barycentric_eval(x) for x in pts]
+            for x, y in zip(pts, oracle_at):
+                check(L.plonk_fr_barycentric(H, bufs[0].ptr, log_n, le32(x), one))
+                assert _un(one.raw) == [y], ("on the domain", log_n, x)
+            ptrs = (ctypes.c_void_p * K)(*[bufs[0].ptr.value] * len(pts) + [b.ptr.value for b in bufs[len(pts):]])
+            check(L.plonk_fr_barycentric_many(H, K, ptrs, log_n, b"".join(le32(x) for x in pts + xs[len(pts):]), out))
+            assert _un(out.raw) == oracle_at + want[len(pts):], ("many, on the domain", log_n)

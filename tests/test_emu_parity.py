@@ -365,3 +365,15 @@ def test_product_verifier(emu):
     from plonkathon_amd import Setup
 
     pc.verifier_cases(Setup.from_file(pc.PTAU))
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+def test_distributed_ntt_every_rank_on_one_device(emu, inverse):
+    """2^16 = 2^8 x 2^8 over 2 and 8 simulated ranks (the sizes up to 2^22 and the extreme inputs: the GPU suite)."""
+    pc.dist_ntt_ranks_on_one_device(16, (1, 3), inverse)
+    pc.dist_ntt_refusals()
+
+
+def test_fr_ops_launch_geometries(emu):
+    """The ragged counts and the two smallest barycentric block sizes (the counts behind the grid cap: the GPU suite)."""
+    pc.fr_ops_launch_geometries(large=False, bary_log_ns=(9, 10))

@@ -99,6 +99,18 @@ def test_round_kernels_vs_oracle():
     pc.round_kernels_vs_oracle((3, 4, 6, 9))
 
 
+def test_batched_operators(setup):
+    """plonk_fr_lincomb, plonk_fr_barycentric_many, Polynomial.view and Setup.commit_many at 8, 64 and 2048 elements."""
+    pc.batched_operators(setup)
+
+
+@pytest.mark.parametrize("part", pc.FR_OPS_PARTS)
+def test_fr_ops_launch_geometries(part):
+    """The streaming kernels of csrc/fr_ops.hip at ragged counts and behind the 2048-workgroup cap of their grids (a second, partial
+    grid-stride iteration), in place where the ABI allows it; barycentric at every block size and in its multi-chunk loop."""
+    pc.fr_ops_launch_geometries(parts=(part,))
+
+
 def test_poly_asserts():
     pc.poly_asserts()
 
@@ -300,13 +312,7 @@ def test_ntt_exact_vs_c_oracle(log_n):
     assert pc.ints(pc.P(v, Basis.LAGRANGE).ifft()) == c_oracle.fr_ntt(v, True)
 
 
-def _random_canonical_bytes(seed, n):
-    """n canonical elements (< 2^253 < r) as 32-byte little-endian words, from a seeded numpy generator."""
-    import numpy as np
-
-    a = np.random.default_rng(seed).integers(0, 256, size=(n, 32), dtype=np.uint8)
-    a[:, 31] &= 0x1F
-    return a.tobytes()
+_random_canonical_bytes = pc.random_canonical_bytes
 
 
 @pytest.mark.parametrize("log_n,split", [(24, 0), (24, 13), (24, 12), (23, 0)])
@@ -758,3 +764,28 @@ def test_wave_kernel_two_pass_splits_and_batches(log_n, split):
 def test_bls12_381_golden_vectors():
     """The committed known-answer vectors of the BLS12-381 scalar-field transforms (definition in Python integers), 2^8 .. 2^16."""
     pc.bls_golden(max_log_n=16)
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("log_n", [16, 17, 18, 19, 20, 21, 22])
+def test_distributed_ntt_every_rank_on_one_device(log_n, inverse):
+    """plonk_fr_ntt_dist_columns / _rows with MORE than one rank: every rank's local passes in turn on this device, the
+    all-to-all between them as device copies — W = 2, 4 and the plan's maximum for the size, exact against the C oracle.  The
+    default splits of 2^16 .. 2^22 run the 2^8, 2^10 and 2^11 wave kernels as column pass and 2^8, 2^9, 2^10 and 2^11 as row pass."""
+    pc.dist_ntt_ranks_on_one_device(log_n, sorted({1, 2, pc.dist_max_log_world(log_n)}), inverse)
+
+
+@pytest.mark.parametrize("data", ["zero", "max", "last", "alt"])
+def test_distributed_ntt_extreme_inputs_at_the_most_ranks(data):
+    """All zero, every element r - 1, a lone r - 1 at the last index, alternating 1 and r - 1: 2^16 and 2^18 over as many ranks
+    as the plan admits, both directions."""
+    for log_n in (16, 18):
+        for inverse in (False, True):
+            pc.dist_ntt_ranks_on_one_device(log_n, (pc.dist_max_log_world(log_n),), inverse, data)
+
+
+def test_distributed_ntt_refusals():
+    pc.dist_ntt_refusals()
+    # the kernels the sizes of test_distributed_ntt_every_rank_on_one_device cover between them: column passes, row passes
+    splits = [pc.dist_split(log_n) for log_n in range(16, 23)]
+    assert {a for a, _ in splits} >= {8, 10, 11} and {b for _, b in splits} >= {8, 9, 10, 11}, splits
