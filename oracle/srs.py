@@ -12,6 +12,9 @@ SETUP_FILE_G1_STARTPOS = 80  # setup.py:11
 SETUP_FILE_POWERS_POS = 60  # setup.py:12
 # py_ecc.bn128.G2 x-coordinate, c0 coefficient (published constant)
 G2_X_C0 = 10857046999023057135944570762232829481370756359578518086990519993285655852781
+# The secret of `Setup.from_tau` in this repository's tests and fixtures (decimal digits of pi).  It is public, so an SRS built
+# from it is worthless as a trusted setup: test vectors for group orders above the 2^11 powers of tests/golden/srs_2048.ptau only.
+TEST_TAU = 314159265358979323846264338327950288419716939937510582097494459230781640628
 
 
 class Setup:
@@ -46,6 +49,24 @@ class Setup:
     def from_file(cls, filename):
         with open(filename, "rb") as f:
             return cls.from_bytes(f.read())
+
+    @classmethod
+    def from_tau(cls, tau: int, n_powers: int):
+        """An SRS from a KNOWN secret: [tau^i] G for i < n_powers and X2 = tau G2.  FOR TESTS ONLY — whoever knows tau can
+        forge openings, so such a setup proves nothing to anyone; it exists because no ceremony file in this repository has
+        more than 2^11 powers and the prover is documented up to 2^12.  Each power is one scalar multiplication in the C half of
+        the oracle (about two seconds for 4096 powers); X2 goes through the Python pairing module's G2 arithmetic."""
+        from . import c_oracle, pairing
+        from .field import R_MOD
+
+        tau %= R_MOD
+        assert tau > 1 and n_powers >= 1
+        powers_of_x, t = [], 1
+        for _ in range(n_powers):
+            powers_of_x.append(c_oracle.g1_lincomb([G1], [t]))
+            t = t * tau % R_MOD
+        x2 = pairing.multiply(pairing.G2, tau)
+        return cls(powers_of_x, ((x2[0].c[0], x2[0].c[1]), (x2[1].c[0], x2[1].c[1])))
 
     def commit(self, values: Polynomial):
         """setup.py:66-72."""

@@ -856,24 +856,240 @@ def batch_prover_rejects_bad_witness(setup):
         bp.prove({"a": 3, "b": 4})
 
 
-def batch_prover_fixture_cases(setup, names, batch_copies=1):
-    """group_order 2^10 / 2^11 proofs against tests/golden/oracle_proofs.json."""
-    fx = {c["name"]: c for c in load("oracle_proofs.json")["cases"]}
+def fixture_case(name):
+    """A case of tests/golden/oracle_proofs.json (tools/gen_oracle_proofs.py) with its program lines."""
+    case = {c["name"]: c for c in load("oracle_proofs.json")["cases"]}[name]
+    n = case["group_order"]
+    return case, (chain_lines(n) if case["program"] == "chain" else poseidon_program_lines())
+
+
+def assert_matches_fixture(got, case, tag=None):
+    """`got` = flat(proof): every commitment and evaluation of the fixture's proof."""
+    for k, v in case["proof"].items():
+        want = pt(v) if isinstance(v, list) else int(v)
+        assert got[k] == want, (case["name"], tag, k)
+
+
+def batch_prover_fixture_cases(setup, names, batch_copies=1, setup_for=None):
+    """group_order 2^9 .. 2^12 proofs against tests/golden/oracle_proofs.json.  A case proved on another SRS than the committed
+    .ptau names it ("srs_tau": the secret of oracle.srs.Setup.from_tau): `setup_for(case)` then returns the Setup to prove on
+    (tau_setups below); without it every case runs on `setup`, and a case that names an SRS is refused."""
     for name in names:
-        case = fx[name]
+        case, lines = fixture_case(name)
         n = case["group_order"]
-        lines = chain_lines(n) if case["program"] == "chain" else poseidon_program_lines()
+        assert setup_for is not None or "srs_tau" not in case, "%s was proved on an SRS of its own: pass setup_for" % name
         program = Program(lines, n)
         wit = program.fill_variable_assignments({k: int(v) for k, v in case["start"].items()})
-        bp = pa.BatchProver(setup, program)
+        bp = pa.BatchProver(setup_for(case) if setup_for else setup, program)
         proofs = bp.prove_batch([dict(wit) for _ in range(batch_copies)])
         for b, proof in enumerate(proofs):
-            got = flat(proof)
-            for k, v in case["proof"].items():
-                want = pt(v) if isinstance(v, list) else int(v)
-                assert got[k] == want, (name, b, k)
+            assert_matches_fixture(flat(proof), case, b)
             for k, v in bp.challenges(b).items():
                 assert str(v.n) == case["challenges"][k], (name, b, k)
+
+
+# ---- group orders beyond the .ptau, and every transform form under the prover ----------------------------------------------
+# The committed .ptau holds 2^11 powers; the prover is documented up to group_order 2^12.  An SRS of 2^12 powers comes from a
+# secret everybody knows (oracle.srs.TEST_TAU: test vectors only), through the C oracle's scalar multiplication.
+from oracle.srs import TEST_TAU  # noqa: E402
+
+_oracle_tau_setups = {}
+
+
+def oracle_tau_setup(tau=TEST_TAU, n_powers=4096):
+    """oracle.srs.Setup.from_tau, built once per process (about two seconds for 4096 powers)."""
+    key = (int(tau), n_powers)
+    if key not in _oracle_tau_setups:
+        _oracle_tau_setups[key] = OSetup.from_tau(int(tau), n_powers)
+    return _oracle_tau_setups[key]
+
+
+def product_tau_setup(tau=TEST_TAU, n_powers=4096, spot_checks=8):
+    """plonkathon_amd.Setup over the points of oracle_tau_setup, `spot_checks` random powers checked against the Python group
+    law (oracle.g1.multiply: not the code that made them)."""
+    import random
+
+    o = oracle_tau_setup(tau, n_powers)
+    rng = random.Random(4096)
+    for i in rng.sample(range(n_powers), spot_checks):
+        assert o.powers_of_x[i] == og1.multiply(og1.G1, pow(int(tau), i, R_MOD)), i
+    fq2 = lambda c: pa.kzg.Fq2(c)
+    return Setup(powers_of_x=[(Fq(x), Fq(y)) for x, y in o.powers_of_x], X2=(fq2(o.X2[0]), fq2(o.X2[1])))
+
+
+class tau_setups:
+    """setup_for of batch_prover_fixture_cases: the .ptau Setup for a case that names no SRS, the from_tau Setup (built by `make`,
+    called at most once per secret) for one that does."""
+
+    def __init__(self, ptau_setup, make=product_tau_setup):
+        self.ptau_setup, self.make, self.made = ptau_setup, make, {}
+
+    def __call__(self, case):
+        if "srs_tau" not in case:
+            return self.ptau_setup
+        tau = int(case["srs_tau"])
+        if tau not in self.made:
+            self.made[tau] = self.make(tau, case["group_order"])
+        return self.made[tau]
+
+
+# seven distinct witnesses of the chain circuit (x0 public, x_{i+1} = x_i^2): 7 is coprime to every tile, wave and batch size.
+# x0 = 3 first: the one the fixtures and the live oracle cover
+CHAIN_X0S = (3, 4, 77, 12345678901234567890, 0xDEADBEEF12345, R_MOD - 2, 5)
+_oracle_chain_proofs = {}
+_chain_batches = {}
+
+
+def oracle_chain_proof(n, x0):
+    """Proof.flatten() of the oracle prover for the chain circuit on the .ptau, computed once per (n, x0) and process
+    (1 s at n = 64, 2 s at 128, 3.5 s at 256)."""
+    if (n, x0) not in _oracle_chain_proofs:
+        oprog = OProgram(chain_lines(n), n)
+        wit = oprog.fill_variable_assignments({"x0": x0})
+        _oracle_chain_proofs[(n, x0)] = OProver(OSetup.from_file(PTAU), oprog).prove(dict(wit)).flatten()
+    return _oracle_chain_proofs[(n, x0)]
+
+
+def batch_prover_chain_vs_oracle(setup, n, x0s):
+    """batch_prover_vs_oracle for the chain circuit, the oracle's proofs shared between the tests of a process."""
+    program = Program(chain_lines(n), n)
+    wits = [program.fill_variable_assignments({"x0": x0}) for x0 in x0s]
+    got = [flat(p) for p in pa.BatchProver(setup, program).prove_batch(wits)]
+    for x0, g in zip(x0s, got):
+        assert g == oracle_chain_proof(n, x0), (n, x0)
+
+
+def chain_batch(n):
+    """(program, the seven witnesses of CHAIN_X0S, their [7][V] upload blob, the variables in the blob's order), once per n."""
+    if n not in _chain_batches:
+        from plonkathon_amd.batch import _pack_witnesses
+
+        program = Program(chain_lines(n), n)
+        wits = [program.fill_variable_assignments({"x0": x0}) for x0 in CHAIN_X0S]
+        variables = tuple(program.wiring_table()[0])
+        _chain_batches[n] = (program, wits, _pack_witnesses(wits, variables, R_MOD), variables)
+    return _chain_batches[n]
+
+
+def chain_expected_proof_0(n):
+    """What proof 0 (x0 = 3) of the chain circuit must be, as flat() gives it, where a fixture or the live oracle covers it:
+    None at 2^10."""
+    if n in (512, 2048, 4096):
+        proof = fixture_case("chain_%d_x0_3" % n)[0]["proof"]
+        return {k: pt(v) if isinstance(v, list) else int(v) for k, v in proof.items()}
+    if n in (128, 256):
+        return oracle_chain_proof(n, 3)
+    return None
+
+
+def assert_chain_proof_0(n, record):
+    want = chain_expected_proof_0(n)
+    if want is not None:
+        assert flat(pa.BatchProver.decode(record)) == want, n
+
+
+def chain_prove_raw(setup, n, B=7, ctx=None, **kw):
+    """The chain circuit's seven witnesses, cycled to a batch of B, through a fresh BatchProver: (records, status bytes)."""
+    program, _, blob, variables = chain_batch(n)
+    bp = pa.BatchProver(setup, program, ctx, **kw)
+    assert bp.variables == variables
+    per = len(blob) // 7
+    bp.upload_values(b"".join(blob[per * (i % 7):per * (i % 7 + 1)] for i in range(B)) if B != 7 else blob, B)
+    bp.run()
+    return bp.download_raw()
+
+
+def prover_under_ntt_kind(setup, n, kind, reference):
+    """Section "every transform form under the prover": prover_init's and plonk_prover_run's transforms — the fanned, scaled launches
+    no other C-ABI call reaches — on kernel family `kind`; the seven records must be the bytes of `reference` (the default
+    dispatcher's), every status 0, and proof 0 the oracle's where it is known."""
+    from plonkathon_amd import get_context
+    from plonkathon_amd._lib import check
+
+    ctx = get_context()
+    try:
+        check(ctx.L.plonk_ntt_select_kernel(ctx.handle, kind))
+        blob, status = chain_prove_raw(setup, n)
+    finally:
+        check(ctx.L.plonk_ntt_select_kernel(ctx.handle, 0))
+    assert status == bytes(7), (n, kind, list(status))
+    assert len(blob) == 7 * 768
+    for i in range(7):
+        assert blob[768 * i:768 * (i + 1)] == reference[768 * i:768 * (i + 1)], (n, kind, i)
+    assert_chain_proof_0(n, blob[:768])
+
+
+# wave_run / wave_plan_get (csrc/ntt_wave_host.h): latency = batch << log_n <= 2^18 picks the two-element form of 2^9, big =
+# batch << log_n >= 2^20 the 512 x 8 form of 2^12; the prover transforms the wires as 3 B vectors per call and Z and the quotient
+# rows as B.  So at n = 512 the wires leave the two-element form above B = 170 and Z above 512; at n = 4096 the wires reach 512 x 8
+# from B = 86 and Z from 256.  (batch, form of the wire calls, form of the Z / quotient calls):
+DISPATCH_BATCHES = {512: ((7, 2, 2), (200, 8, 2), (600, 8, 8)), 4096: ((7, 4, 4), (100, 8, 4), (300, 8, 8))}
+
+
+def dispatch_form(log_n, batch):
+    """Elements per thread the default dispatcher gives a call of `batch` transforms of 2^log_n (9 or 12): the expressions of
+    wave_run, restated."""
+    if log_n == 9:
+        return 2 if (batch << log_n) <= (1 << 18) else 8
+    assert log_n == 12
+    return 8 if (batch << log_n) >= (1 << 20) else 4
+
+
+for _n, _rows in DISPATCH_BATCHES.items():
+    for _B, _wires, _z in _rows:
+        assert (dispatch_form(_n.bit_length() - 1, 3 * _B), dispatch_form(_n.bit_length() - 1, _B)) == (_wires, _z), (_n, _B)
+
+
+def prover_batch_across_thresholds(setup, n, B, reference, vk):
+    """A batch of B = the seven witnesses cycled, on the default dispatcher: record i is record i mod 7 of the batch of seven
+    (`reference`: no record is left uncompared), proof 0 is the fixture's, the seven are pairwise distinct, every status is 0, and
+    three records at seeded random indices (>= 7 where the batch has them) pass the product's pairing check."""
+    import random
+
+    blob, status = chain_prove_raw(setup, n, B)
+    assert status == bytes(B), [i for i, s in enumerate(status) if s]
+    assert len(blob) == 768 * B and len(reference) == 768 * 7
+    recs = [reference[768 * i:768 * (i + 1)] for i in range(7)]
+    assert len(set(recs)) == 7
+    for i in range(B):
+        assert blob[768 * i:768 * (i + 1)] == recs[i % 7], (n, B, i)
+    assert_chain_proof_0(n, blob[:768])
+    assert chain_expected_proof_0(n) is not None
+    wits = chain_batch(n)[1]
+    rng = random.Random(1000 * n + B)
+    for i in rng.sample(range(7, B) if B >= 10 else range(B), 3):
+        assert vk.verify_proof(n, pa.BatchProver.decode(blob[768 * i:768 * (i + 1)]), [wits[i % 7]["x0"]]), (n, B, i)
+
+
+def proofs_verify_and_reject(setup, lines, group_order, start, public):
+    """proofs_verify with the two rejections spelled out: the GPU's proof passes the ORACLE's pairing-based verifier against a
+    verification key the GPU committed; with one bit of one evaluation flipped it fails, with a wrong public input it fails — under
+    the oracle's verifier and under the product's."""
+    from oracle import pairing
+    from oracle.verifier import VerificationKey
+
+    program = Program(lines, group_order)
+    wit = program.fill_variable_assignments(start)
+    proof = pa.BatchProver(setup, program).prove(dict(wit))
+    fl = flat(proof)
+    vk = setup.verification_key(program.common_preprocessed_input())
+    x2 = (pairing.FQ2([c.n for c in vk.X_2[0].coeffs]), pairing.FQ2([c.n for c in vk.X_2[1].coeffs]))
+    ovk = VerificationKey(group_order, *[affine(getattr(vk, k)) for k in ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")],
+                          x2, vk.w.n)
+    pub = [wit[v] for v in public]
+    assert ovk.verify_proof(group_order, fl, pub)
+    assert vk.verify_proof(group_order, proof, pub)
+    bad = dict(fl)
+    bad["c_eval"] ^= 1 << 100
+    assert not ovk.verify_proof(group_order, bad, pub)
+    import copy
+
+    badp = copy.deepcopy(proof)
+    badp.msg_4.c_eval = Scalar(bad["c_eval"])
+    assert not vk.verify_proof(group_order, badp, pub)
+    wrong = [(pub[0] + 1) % R_MOD] + pub[1:]
+    assert not ovk.verify_proof(group_order, fl, wrong)
+    assert not vk.verify_proof(group_order, proof, wrong)
 
 
 # ------------------------------------------------------------------------------------------ edges / errors

@@ -243,6 +243,24 @@ def test_batch_prover_on_the_wave_kernels(emu):
     pc.batch_prover_vs_oracle(Setup.from_file(pc.PTAU), pc.chain_lines(256), 256, [{"x0": 3}, {"x0": 77}])
 
 
+def test_batch_prover_group_order_2_7(emu):
+    """group_order 2^7: the wave kernel that exists with two elements per thread only, fanned by the prover (three cosets per wire
+    polynomial, the quotient's three slices in place) under the range checks of fpl.h — against the live oracle, two witnesses."""
+    from plonkathon_amd import Setup
+
+    pc.batch_prover_chain_vs_oracle(Setup.from_file(pc.PTAU), 128, [3, 77])
+
+
+@pytest.mark.parametrize("kind", [6, 7])
+def test_batch_prover_group_order_2_9_both_forms(emu, kind):
+    """group_order 2^9 against the fixture, on the eight-element kernel (kind 6) and on the two-element latency form (kind 7: the
+    only place where the fanned two-element 2^9 kernel meets fpl.h's range checks).  2^12 runs on the GPU only."""
+    from plonkathon_amd import Setup
+
+    with pc.ntt_kind(kind):
+        pc.batch_prover_fixture_cases(Setup.from_file(pc.PTAU), ["chain_512_x0_3"])
+
+
 def test_edge_and_error_paths(emu):
     from plonkathon_amd import Setup
 

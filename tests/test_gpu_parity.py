@@ -301,6 +301,132 @@ def test_api_prover_matches_batch_prover_2_11(setup):
     assert pc.flat(p1.prove(dict(wit))) == pc.flat(BatchProver(setup, program).prove(dict(wit)))
 
 
+# ---- lock-step prover: every group order and transform form up to the documented maximum 2^12 -------------------------------
+@pytest.fixture(scope="module")
+def setups(setup):
+    """case -> Setup for the fixtures: the .ptau, or the 2^12 powers of the test-only secret a case names (built on first use,
+    8 random powers checked against the Python group law; the construction time is printed)."""
+    import time
+
+    def make(tau, n_powers):
+        t0 = time.time()
+        s = pc.product_tau_setup(tau, n_powers)
+        print("SRS of %d powers from the test secret: %.2f s on the CPU" % (n_powers, time.time() - t0))
+        return s
+
+    return pc.tau_setups(setup, make)
+
+
+@pytest.fixture(scope="module")
+def setup_for_order(setup, setups):
+    """group order -> the Setup its chain circuit is proved on."""
+    return lambda n: setups(pc.fixture_case("chain_4096_x0_3")[0]) if n > 2048 else setup
+
+
+@pytest.fixture(scope="module")
+def chain_reference(setup_for_order):
+    """n -> the 7 x 768 bytes of pc.CHAIN_X0S' proofs on the default dispatcher and the default table choice, proved once per n:
+    what the forced kernel families and the larger batches must reproduce.  Proof 0 is checked against the oracle here too."""
+
+    done = {}
+
+    def get(n):
+        if n not in done:
+            blob, status = pc.chain_prove_raw(setup_for_order(n), n)
+            assert status == bytes(7), list(status)
+            pc.assert_chain_proof_0(n, blob[:768])
+            done[n] = blob
+        return done[n]
+
+    return get
+
+
+@pytest.mark.parametrize("n", [64, 128])
+def test_prover_orders_vs_live_oracle(setup, n):
+    """2^6: the largest order on the LDS kernel (a fan is a loop of calls); 2^7: the wave kernel with two elements per thread."""
+    pc.batch_prover_chain_vs_oracle(setup, n, [3, 77])
+
+
+@pytest.mark.parametrize("n", [512, 4096])
+def test_prover_orders_fixture(setups, n):
+    """The oracle's proof and challenges, in a batch of three copies.  At 2^12 on the library's default table choice for a base set
+    that is not the 2^11 SRS: the table must really be attached (its build time is printed)."""
+    case = pc.fixture_case("chain_%d_x0_3" % n)[0]
+    pc.batch_prover_fixture_cases(None, [case["name"]], batch_copies=3, setup_for=setups)
+    if n == 4096:
+        info = setups(case).device_bases().lookup_info()
+        print("default lookup table over 4096 bases:", info)
+        assert info["layout"] == "comb" and info["bits"] >= 8 and info["bytes"] >= 4096 * 64 << (info["bits"] - 1), info
+
+
+@pytest.mark.parametrize("n", [512, 4096])
+def test_prover_orders_api_prover_matches_batch_prover(setup_for_order, n):
+    """test_api_prover_matches_batch_prover_2_11 at 2^9 and 2^12."""
+    from plonkathon_amd import BatchProver, Prover
+
+    program, wits = pc.chain_batch(n)[:2]
+    p1 = Prover(setup_for_order(n), program)
+    p1.check = False
+    assert pc.flat(p1.prove(dict(wits[0]))) == pc.flat(BatchProver(setup_for_order(n), program).prove(dict(wits[0])))
+
+
+@pytest.mark.parametrize("n", [512, 4096])
+def test_prover_orders_lagrange_commits(setup_for_order, chain_reference, n):
+    """PLONK_PROVER_LAGRANGE_COMMITS (at 2^12: a 2^12 Lagrange view of the 4096 bases) gives the same bytes."""
+    blob, status = pc.chain_prove_raw(setup_for_order(n), n, lagrange_commits=True)
+    assert status == bytes(7) and blob == chain_reference(n)
+
+
+@pytest.mark.parametrize("n", [512, 4096])
+def test_prover_orders_proofs_verify(setup_for_order, n):
+    """A second witness under the oracle's pairing check; one flipped evaluation bit and a wrong public input are rejected."""
+    pc.proofs_verify_and_reject(setup_for_order(n), pc.chain_lines(n), n, {"x0": 0xDEADBEEF12345}, ["x0"])
+
+
+def test_prover_2_12_lookup_and_bucket_methods_agree(setup_for_order, chain_reference):
+    """MSMs over 4096 bases at stride 4n: 8 witnesses byte-identical from the default table and from the bucket method."""
+    from plonkathon_amd import Context
+
+    n = 4096
+    ref = chain_reference(n)
+    blob, status = pc.chain_prove_raw(setup_for_order(n), n, 8)
+    assert status == bytes(8) and blob == ref + ref[:768]
+    assert setup_for_order(n).device_bases().lookup_info()["layout"] == "comb"
+    c = Context(0)
+    c.msm_lookup(1)
+    bucket, status = pc.chain_prove_raw(setup_for_order(n), n, 8, ctx=c)
+    assert setup_for_order(n).device_bases(c).lookup_info()["layout"] is None
+    assert status == bytes(8) and bucket == blob
+
+
+@pytest.mark.parametrize("kind", [1, 6, 7, 8])
+@pytest.mark.parametrize("n", [128, 256, 512, 1024, 2048, 4096])
+def test_prover_on_every_transform_form(setup_for_order, chain_reference, n, kind):
+    """Kind 1: every fan as a loop of calls on the LDS kernel; 6: eight elements at 2^9, 512 x 8 at 2^12; 7: two elements at 2^9;
+    8: 1024 x 4 at 2^12 — seven proofs byte-identical to the default dispatcher's, proof 0 the oracle's (all sizes but 2^10)."""
+    pc.prover_under_ntt_kind(setup_for_order(n), n, kind, chain_reference(n))
+
+
+@pytest.fixture(scope="module")
+def chain_vk(setup_for_order):
+    """n -> the verification key of the chain circuit, committed once per n."""
+    done = {}
+
+    def get(n):
+        if n not in done:
+            done[n] = setup_for_order(n).verification_key(pc.chain_batch(n)[0].common_preprocessed_input())
+        return done[n]
+
+    return get
+
+
+@pytest.mark.parametrize("n,B", [(n, row[0]) for n, rows in pc.DISPATCH_BATCHES.items() for row in rows])
+def test_prover_batches_across_dispatcher_thresholds(setup_for_order, chain_reference, chain_vk, n, B):
+    """pc.DISPATCH_BATCHES: batches on both sides of the thresholds where the default dispatcher changes the kernel form of 2^9 and
+    2^12, including the batches that mix two forms within one proof."""
+    pc.prover_batch_across_thresholds(setup_for_order(n), n, B, chain_reference(n), chain_vk(n))
+
+
 @pytest.mark.parametrize("log_n", [16, 17, 18, 19, 20, 21, 22])
 def test_ntt_exact_vs_c_oracle(log_n):
     """Bit-exact forward and inverse transforms at microbench sizes against the C half of the oracle."""
