@@ -223,7 +223,9 @@ int plonk_srs_lookup_top(const plonk_srs* srs, unsigned* out_top_bits, unsigned*
  *   plonk_prover_create   Prover(setup, program): `selectors_le32` = the eight CommonPreprocessedInput
  *                         vectors QM, QL, QR, QO, QC, S1, S2, S3 (compiler/program.py:10-30), each
  *                         2^log_n canonical Fr values; n_public = len(program.get_public_assignments()).
- *                         Extends the circuit polynomials to the quotient coset once.
+ *                         Extends the circuit polynomials to the quotient coset once.  1 <= log_n <= 16; a batch
+ *                         takes 32 vectors of 2^log_n 32-byte elements per proof (2^16: 64 MiB), and an upload that
+ *                         does not fit returns PLONK_ERR_NOMEM with the bytes it wanted.
  *   plonk_prover_upload_witness   the wire columns A, B, C of round 1 (prover.py:94-103) laid out
  *                         [3][batch][n] and the public inputs [batch][n_public] (PI = -public,
  *                         prover.py:57-62), canonical LE; they stay resident in HBM.
@@ -245,6 +247,13 @@ int plonk_prover_destroy(plonk_prover* p);
 /* options (0 = default): PLONK_PROVER_LAGRANGE_COMMITS commits a_1, b_1, c_1 and z_1 (rounds 1-2) from their
  * Lagrange values over plonk_srs_lagrange instead of from coefficient forms — same group elements, same proof. */
 #define PLONK_PROVER_LAGRANGE_COMMITS 1u
+/* PLONK_PROVER_SEGMENTS_LOG2(k), tests and A/B runs: the three per-proof scans (round 2's grand product, round 4's evaluations,
+ * round 5's two divisions) run cut into S = 2^k segments per proof, each as two or three launches over (S, batch) workgroups,
+ * instead of one workgroup per proof; k = 0 forces the one-workgroup kernels.  Bits 8-11 hold k + 1; zero there = automatic
+ * (plonk_prover_plan_segments: S > 1 only where `batch` workgroups leave the chip idle and the circuit is large).  Same proofs,
+ * bit for bit.  PLONK_ERR_ARG for S > 256, for segments of fewer than 16 rows, and for any bit outside the two options. */
+#define PLONK_PROVER_SEGMENTS_LOG2(k) ((((unsigned)(k) + 1u) & 15u) << 8)
+#define PLONK_PROVER_SEGMENTS_MASK (15u << 8)
 int plonk_prover_set_options(plonk_prover* p, unsigned flags);
 int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t batch);
 /* The same inputs at n_vars * 32 bytes per proof instead of 3 * n * 32: the wiring is given once per circuit —
@@ -417,6 +426,9 @@ int plonk_ntt_set_split(plonk_ctx* ctx, unsigned log_n, unsigned log_r1);
 int plonk_ntt_get_split(plonk_ctx* ctx, unsigned log_n, unsigned* out_log_r1);
 /* tuning knobs (0 = library default): window bits c and window-groups per MSM (bucket method) */
 int plonk_msm_configure(plonk_ctx* ctx, unsigned window_bits, unsigned groups);
+/* the number of segments the lock-step prover (and plonk_fr_grand_product, batch = 1) cuts the per-proof scans of `batch` proofs
+ * of 2^log_n rows into on ctx's device when PLONK_PROVER_SEGMENTS_LOG2 is not set: 1 = one workgroup per proof */
+int plonk_prover_plan_segments(plonk_ctx* ctx, unsigned log_n, size_t batch, unsigned* out_segments);
 
 /* ---- timing support for bench.py (HIP events on the context's stream) ------------------------ */
 int plonk_timer_start(plonk_ctx* ctx);

@@ -36,11 +36,13 @@ except ImportError:  # pragma: no cover - pure-Python equivalent of the packer (
 
 
 class BatchProver:
-    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False):
+    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False, segments=None):
         """`ctx`: the Context (HIP stream) to run on; several BatchProvers on distinct contexts of one
         GPU overlap each other's latency-bound kernels (transcript, inversions) with MSM work.
         `lagrange_commits`: commit a_1, b_1, c_1, z_1 from Lagrange values over the Lagrange-basis SRS
-        (PLONK_PROVER_LAGRANGE_COMMITS) instead of from coefficient forms; same proofs."""
+        (PLONK_PROVER_LAGRANGE_COMMITS) instead of from coefficient forms; same proofs.
+        `segments`: None = automatic (`segments_for`); a power of two S forces the per-proof scans of rounds 2, 4 and 5 to run
+        cut into S segments per proof (PLONK_PROVER_SEGMENTS_LOG2; 1 = one workgroup per proof): tests and A/B runs, same proofs."""
         self.group_order = program.group_order
         self.setup = setup
         self.program = program
@@ -60,8 +62,13 @@ class BatchProver:
         check(self.ctx.L.plonk_prover_create(self.ctx.handle, self._bases.handle, _log2_exact(n), sel,
                                              len(self._public_vars), ctypes.byref(self._h)))
         self._resident = 0
-        if lagrange_commits:
-            check(self.ctx.L.plonk_prover_set_options(self._h, 1))
+        flags = 1 if lagrange_commits else 0
+        if segments is not None:
+            if segments < 1 or segments & (segments - 1):
+                raise ValueError("segments must be a power of two")
+            flags |= min(segments.bit_length(), 15) << 8  # k + 1 in bits 8-11; the library checks the range
+        if flags:
+            check(self.ctx.L.plonk_prover_set_options(self._h, flags))
         # the wiring goes to the device once; a batch is then only the variables' values (V x 32 B per proof)
         self._getter = None
         if self._vars:
@@ -79,6 +86,12 @@ class BatchProver:
                 self._h = None
         except Exception:
             pass
+
+    def segments_for(self, B):
+        """The number of segments per proof a batch of B runs its per-proof scans in when `segments` was not given."""
+        out = ctypes.c_uint(0)
+        check(self.ctx.L.plonk_prover_plan_segments(self.ctx.handle, _log2_exact(self.group_order), B, ctypes.byref(out)))
+        return out.value
 
     # ---- inputs ---------------------------------------------------------------------------------
     def wire_columns(self, witness):

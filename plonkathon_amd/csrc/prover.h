@@ -34,6 +34,7 @@ constexpr size_t proof_bytes(bool compressed) { return compressed ? PROOF_BYTES_
 
 #define PI_SPARSE_MAX 8
 enum { FX_QM = 0, FX_QL, FX_QR, FX_QO, FX_QC, FX_S1, FX_S2, FX_S3, FX_COUNT };
+#define PROVER_MAX_LOG_N 16  // the largest group order the lock-step prover accepts: what the suite checks (tests/test_gpu_prover_large.py)
 #define QCOSETS 3  // cosets of size n the lock-step prover evaluates the quotient on (deg t < 3n)
 
 struct plonk_prover {
@@ -72,6 +73,10 @@ struct plonk_prover {
     uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
     Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
     struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
+    // the segmented scans (prover.hip): carries and partial sums of the S segments of every proof, none while S = 1
+    Fr* seg;                   // [7 B S + B]
+    size_t seg_cap;            // elements
+    unsigned seg_forced;       // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
     // wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device
     uint32_t* cell_index;      // [3][n]  variable index of each wire cell; n_vars = empty cell / padding row
     uint32_t* pub_index;       // [n_public]

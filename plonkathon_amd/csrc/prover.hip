@@ -485,6 +485,282 @@ __global__ void __launch_bounds__(DV_THREADS) divide_linear_kernel(const Fr* p_i
 }
 
 // ------------------------------------------------------------------------------------------------
+// Segmented forms of the three per-proof scans (grand product, evaluations, division by X - x0) for batches too small to fill the
+// chip with one workgroup per proof.  A proof's n rows are cut into S equal segments (S a power of two, 2 <= S <= 256,
+// n / S >= 16) and every scan becomes three launches, or two, on the prover's stream: per-segment work on a grid of (S, B)
+// workgroups, a small per-proof launch that turns the S segment totals into carries, and a second (S, B) launch that applies
+// them.  The launches are ordered by the stream alone: no workgroup ever waits for another inside a kernel.  Everything is a
+// canonical residue of an associative operation, so the results are the bits the one-workgroup kernels above (S = 1) give.
+// n and S are powers of two, so a segment's L = n / S rows fall on its 256 lanes as `per` = max(L / 256, 1) rows each: lanes
+// below min(L, 256) hold exactly `per` rows, the others none, and an empty lane carries the scan's neutral element.
+#define SEG_THREADS 256
+struct SegRange { size_t lo, hi, per; };
+PLONK_DEV SegRange seg_lane_range(size_t n, unsigned S, unsigned seg, unsigned tid) {
+    const size_t L = n / S, per = (L + SEG_THREADS - 1) / SEG_THREADS, s_lo = (size_t)seg * L, s_hi = s_lo + L;
+    SegRange r;
+    r.per = per;
+    r.lo = s_lo + (size_t)tid * per < s_hi ? s_lo + (size_t)tid * per : s_hi;
+    r.hi = r.lo + per < s_hi ? r.lo + per : s_hi;
+    return r;
+}
+
+// Grand product, launch 1 of 3, grid (S, B): the factors of the segment's rows into num_buf / den_buf (grand_product_kernel's
+// pass 1), and the segment's two products into seg_n / seg_d [B][S].
+__global__ void __launch_bounds__(SEG_THREADS) gp_seg_factors_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
+                                                                     RoundChallenges direct, size_t n, Fr* num_buf, Fr* den_buf,
+                                                                     Fr* seg_n, Fr* seg_d) {
+    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
+    const size_t b = blockIdx.y;
+    const unsigned tid = threadIdx.x, S = gridDim.x;
+    const Fr beta = st ? st[b].beta : direct.beta, gamma = st ? st[b].gamma : direct.gamma;
+    const Fr *A = in.abc[0] + b * n, *Bv = in.abc[1] + b * n, *C = in.abc[2] + b * n;
+    const Fr *S1 = in.sig[0], *S2 = in.sig[1], *S3 = in.sig[2];
+    Fr *NUM = num_buf + b * n, *DEN = den_buf + b * n;
+    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
+    const Fr one = fp_one<FrParams>();
+    Fr pn = one, pd = one;
+    for (size_t i = r.lo; i < r.hi; i++) {
+        Fr a = fp_load(A + i), bb = fp_load(Bv + i), c = fp_load(C + i);
+        Fr bw = fp_mul(beta, fp_load(roots + i));
+        Fr ag = fp_add(a, gamma), bg = fp_add(bb, gamma), cg = fp_add(c, gamma);
+        Fr num = fp_mul(fp_mul(fp_add(ag, bw), fp_add(bg, fp_dbl(bw))), fp_add(cg, fp_mul3(bw)));
+        Fr den = fp_mul(fp_mul(fp_add(ag, fp_mul(beta, fp_load(S1 + i))), fp_add(bg, fp_mul(beta, fp_load(S2 + i)))),
+                        fp_add(cg, fp_mul(beta, fp_load(S3 + i))));
+        if (fp_is_zero(den)) {  // ratio num/0 == 0 (py_ecc): the factor leaves the denominator products
+            num = fp_zero<FrParams>();
+            den = one;
+        }
+        fp_store(NUM + i, num);
+        fp_store(DEN + i, den);
+        pd = fp_mul(pd, den);
+        pn = fp_mul(pn, num);
+    }
+    sc_n[tid] = pn;
+    sc_d[tid] = pd;
+    __syncthreads();
+    for (unsigned s = SEG_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            sc_n[tid] = fp_mul(sc_n[tid], sc_n[tid + s]);
+            sc_d[tid] = fp_mul(sc_d[tid], sc_d[tid + s]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        fp_store(seg_n + b * S + blockIdx.x, sc_n[0]);
+        fp_store(seg_d + b * S + blockIdx.x, sc_d[0]);
+    }
+}
+
+// Launch 2 of 3, one workgroup per proof, lane s = segment s: seg_n[s] <- prod of the numerators BEFORE segment s, seg_d[s] <-
+// prod of the denominators AFTER it, tot_inv[b] = the proof's one inversion, closes[b].
+__global__ void __launch_bounds__(SEG_THREADS) gp_seg_carries_kernel(unsigned S, Fr* seg_n, Fr* seg_d, Fr* tot_inv, uint32_t* closes) {
+    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
+    const size_t b = blockIdx.x;
+    const unsigned tid = threadIdx.x;
+    const Fr one = fp_one<FrParams>();
+    sc_n[tid] = tid < S ? fp_load(seg_n + b * S + tid) : one;
+    sc_d[tid] = tid < S ? fp_load(seg_d + b * S + tid) : one;
+    __syncthreads();
+    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {  // inclusive prefix of sc_n, inclusive suffix of sc_d
+        Fr vn = sc_n[tid], vd = sc_d[tid];
+        if (tid >= off) vn = fp_mul(vn, sc_n[tid - off]);
+        if (tid + off < SEG_THREADS) vd = fp_mul(vd, sc_d[tid + off]);
+        __syncthreads();
+        sc_n[tid] = vn;
+        sc_d[tid] = vd;
+        __syncthreads();
+    }
+    if (tid < S) {
+        fp_store(seg_n + b * S + tid, tid ? sc_n[tid - 1] : one);
+        fp_store(seg_d + b * S + tid, tid + 1 < SEG_THREADS ? sc_d[tid + 1] : one);
+    }
+    if (tid == 0) {
+        const Fr tinv = fp_inv(sc_d[0]);  // product of all non-zero denominators
+        fp_store(tot_inv + b, tinv);
+        closes[b] = fp_eq(fp_mul(sc_n[SEG_THREADS - 1], tinv), one) ? 1u : 0u;  // prover.py:132
+    }
+}
+
+// Launch 3 of 3, grid (S, B): grand_product_kernel's passes 2 and 3 inside the segment, seeded with its carries.
+__global__ void __launch_bounds__(SEG_THREADS) gp_seg_apply_kernel(size_t n, const Fr* seg_n, const Fr* seg_d, const Fr* tot_inv,
+                                                                   const Fr* num_buf, Fr* den_buf, Fr* z_out) {
+    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
+    const size_t b = blockIdx.y;
+    const unsigned tid = threadIdx.x, S = gridDim.x;
+    const Fr* NUM = num_buf + b * n;
+    Fr* DEN = den_buf + b * n;
+    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
+    const Fr one = fp_one<FrParams>();
+    Fr pn = one, pd = one;
+    for (size_t i = r.lo; i < r.hi; i++) {
+        pn = fp_mul(pn, fp_load(NUM + i));
+        pd = fp_mul(pd, fp_load(DEN + i));
+    }
+    sc_n[tid] = pn;
+    sc_d[tid] = pd;
+    __syncthreads();
+    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
+        Fr vn = sc_n[tid], vd = sc_d[tid];
+        if (tid >= off) vn = fp_mul(vn, sc_n[tid - off]);
+        if (tid + off < SEG_THREADS) vd = fp_mul(vd, sc_d[tid + off]);
+        __syncthreads();
+        sc_n[tid] = vn;
+        sc_d[tid] = vd;
+        __syncthreads();
+    }
+    Fr run_n = fp_load(seg_n + b * S + blockIdx.x), after_d = fp_load(seg_d + b * S + blockIdx.x);
+    if (tid) run_n = fp_mul(run_n, sc_n[tid - 1]);
+    if (tid + 1 < SEG_THREADS) after_d = fp_mul(after_d, sc_d[tid + 1]);
+    const Fr tinv = fp_load(tot_inv + b);
+    for (size_t k = r.hi; k-- > r.lo;) {  // DEN[k] <- prod_{j >= k} den_j
+        after_d = fp_mul(after_d, fp_load(DEN + k));
+        fp_store(DEN + k, after_d);
+    }
+    for (size_t i = r.lo; i < r.hi; i++) {  // Z_i = PN_i * SD_i * tot_inv
+        fp_store(z_out + b * n + i, fp_mul(fp_mul(run_n, fp_load(DEN + i)), tinv));
+        run_n = fp_mul(run_n, fp_load(NUM + i));
+    }
+}
+
+// Evaluations, launch 1 of 2, grid (S, B): eval_kernel's blocked Horner over the segment's rows, every lane's chains scaled by
+// x^(global chunk start); the segment's seven sums go to part[b][s][NEVAL].
+__global__ void __launch_bounds__(SEG_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, Fr w, const ProofState* st,
+                                                               size_t n, size_t B, Fr* part) {
+    __shared__ Fr red[NEVAL][SEG_THREADS];
+    const size_t b = blockIdx.y;
+    const unsigned tid = threadIdx.x, S = gridDim.x;
+    const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
+    const Fr* polys[NEVAL] = {coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
+                              fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (4 * B + b) * n,
+                              coef + (3 * B + b) * n};
+    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
+    const Fr shift_z = fp_pow_u64(zeta, (uint64_t)r.lo), shift_zw = fp_pow_u64(zeta_w, (uint64_t)r.lo);
+    typedef FpL<FrParams> L;
+    const L zl = fpl_from_fp_uniform(zeta), zwl = fpl_from_fp_uniform(zeta_w);
+    L acc[NEVAL];
+    wave_for<NEVAL>([&](auto P_) { acc[decltype(P_)::value] = fpl_zero<FrParams>(); });
+#pragma unroll 1
+    for (size_t i = r.hi; i-- > r.lo;)
+        wave_for<NEVAL>([&](auto P_) {
+            constexpr unsigned p = decltype(P_)::value;
+            acc[p] = fpl_add(fpl_mul(acc[p], p == 5 ? zwl : zl), fpl_from_fp(fp_load(polys[p] + i)));  // (-m, 3m), limbs < 2^30
+        });
+    const L sh_z = fpl_from_fp(shift_z), sh_zw = fpl_from_fp(shift_zw);
+    wave_for<NEVAL>([&](auto P_) {
+        constexpr unsigned p = decltype(P_)::value;
+        red[p][tid] = r.lo < r.hi ? fpl_pack_canonical(fpl_mul(acc[p], p == 5 ? sh_zw : sh_z)) : fp_zero<FrParams>();
+    });
+    __syncthreads();
+    for (unsigned s = SEG_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int p = 0; p < NEVAL; p++) red[p][tid] = fp_add(red[p][tid], red[p][tid + s]);
+        __syncthreads();
+    }
+    if (tid < NEVAL) fp_store(part + (b * S + blockIdx.x) * NEVAL + tid, red[tid][0]);
+}
+
+// Launch 2 of 2, one workgroup per proof: lane group p (32 lanes) adds the S partial sums of evaluation p into st[b].evals[p].
+__global__ void __launch_bounds__(SEG_THREADS) eval_seg_finish_kernel(const Fr* part, unsigned S, ProofState* st) {
+    __shared__ Fr red[SEG_THREADS];
+    const size_t b = blockIdx.x;
+    const unsigned tid = threadIdx.x, p = tid / 32, l = tid % 32;
+    Fr acc = fp_zero<FrParams>();
+    if (p < NEVAL)
+        for (unsigned s = l; s < S; s += 32) acc = fp_add(acc, fp_load(part + (b * S + s) * NEVAL + p));
+    red[tid] = acc;
+    __syncthreads();
+    for (unsigned s = 16; s > 0; s >>= 1) {
+        if (l < s) red[tid] = fp_add(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    if (l == 0 && p < NEVAL) st[b].evals[p] = red[tid];
+}
+
+// Division by X - x0, both openings at once: blockIdx.z = 0 divides p_in[0] by X - zeta, 1 divides p_in[1] by X - zeta w.
+struct DivideIn { const Fr* p_in[2]; Fr* q_out[2]; };
+// the lane's Horner value h = sum_{i in chunk} p_i x0^(i - lo)
+PLONK_DEV Fr divide_chunk_horner(const Fr* p, const SegRange& r, const Fr& x0) {
+    Fr h = fp_zero<FrParams>();
+    for (size_t i = r.hi; i-- > r.lo;) h = fp_add(fp_mul(h, x0), fp_load(p + i));
+    return h;
+}
+// Launch 1 of 3, grid (S, B, 2): the segment's Horner value H_s = sum_{i in segment} p_i x0^(i - segment start) into seg_h[z][b][s].
+__global__ void __launch_bounds__(SEG_THREADS) divide_seg_horner_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
+    __shared__ Fr sc[SEG_THREADS];
+    const size_t b = blockIdx.y, B = gridDim.y;
+    const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
+    Fr x0 = st[b].zeta;
+    if (z) x0 = fp_mul(x0, w);
+    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
+    sc[tid] = divide_chunk_horner(in.p_in[z] + b * n, r, x0);
+    __syncthreads();
+    Fr m = fp_pow_u64(x0, (uint64_t)r.per);  // x0^(per * off)
+    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
+        if ((tid & (2 * off - 1)) == 0) sc[tid] = fp_add(sc[tid], fp_mul(m, sc[tid + off]));
+        m = fp_sqr(m);
+        __syncthreads();
+    }
+    if (tid == 0) fp_store(seg_h + ((size_t)z * B + b) * S + blockIdx.x, sc[0]);
+}
+
+// Launch 2 of 3, grid (B, 1, 2), lane s = segment s: the suffix scan over segments under (a, m) o (b, m') = (a + m b, m m') with
+// m = x0^(n / S); seg_h[s] <- the carry entering segment s, q at the segment's last index = sum_{j >= segment end} p_j x0^(j - end).
+__global__ void __launch_bounds__(SEG_THREADS) divide_seg_carries_kernel(unsigned S, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
+    __shared__ Fr sc[SEG_THREADS];
+    const size_t b = blockIdx.x, B = gridDim.x;
+    const unsigned tid = threadIdx.x, z = blockIdx.z;
+    Fr x0 = st[b].zeta;
+    if (z) x0 = fp_mul(x0, w);
+    Fr* h = seg_h + ((size_t)z * B + b) * S;
+    sc[tid] = tid < S ? fp_load(h + tid) : fp_zero<FrParams>();
+    __syncthreads();
+    Fr m = fp_pow_u64(x0, (uint64_t)(n / S));
+    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
+        Fr vv = sc[tid];
+        if (tid + off < SEG_THREADS) vv = fp_add(vv, fp_mul(m, sc[tid + off]));
+        __syncthreads();
+        sc[tid] = vv;
+        m = fp_sqr(m);
+        __syncthreads();
+    }
+    if (tid < S) fp_store(h + tid, tid + 1 < SEG_THREADS ? sc[tid + 1] : fp_zero<FrParams>());
+}
+
+// Launch 3 of 3, grid (S, B, 2): divide_linear_kernel inside the segment; the segment's carry enters its last lane, as the value
+// one chunk above that lane's rows.
+__global__ void __launch_bounds__(SEG_THREADS) divide_seg_apply_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, const Fr* seg_h) {
+    __shared__ Fr sc[SEG_THREADS];
+    const size_t b = blockIdx.y, B = gridDim.y;
+    const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
+    Fr x0 = st[b].zeta;
+    if (z) x0 = fp_mul(x0, w);
+    const Fr* p = in.p_in[z] + b * n;
+    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
+    const size_t L = n / S;
+    const unsigned last = (unsigned)(L < SEG_THREADS ? L : SEG_THREADS) - 1;  // the last lane that holds rows
+    const Fr carry = fp_load(seg_h + ((size_t)z * B + b) * S + blockIdx.x);
+    Fr m = fp_pow_u64(x0, (uint64_t)r.per);
+    Fr h = divide_chunk_horner(p, r, x0);
+    if (tid == last) h = fp_add(h, fp_mul(m, carry));
+    sc[tid] = h;
+    __syncthreads();
+    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
+        Fr vv = sc[tid];
+        if (tid + off < SEG_THREADS) vv = fp_add(vv, fp_mul(m, sc[tid + off]));
+        __syncthreads();
+        sc[tid] = vv;
+        m = fp_sqr(m);
+        __syncthreads();
+    }
+    Fr q = tid < last ? sc[tid + 1] : carry;
+    Fr* out = in.q_out[z] + b * n;
+    for (size_t i = r.hi; i-- > r.lo;) {
+        fp_store(out + i, q);                       // q_i
+        q = fp_add(fp_load(p + i), fp_mul(x0, q));  // q_{i-1} = p_i + x0 q_i
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // pack results: [B] proof records (prover.h), plain or compressed
 __global__ void pack_proofs_kernel(const Fq* commit_xy, const ProofState* st, size_t B, uint8_t* out, int compressed) {
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -529,7 +805,64 @@ __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes,
 
 // ================================================================================================
 // host side
+
+// How many segments S the three per-proof scans are cut into for `B` proofs of 2^log_n rows on a device of `cus` compute units
+// (1: the one-workgroup kernels).  Measured on an MI355X, 256 CUs (profiles/prover_large.json, tools/prover_scale.py; the table
+// is in DESIGN.md 4.3), the three scans together, per plonk_prover_run:
+//   * SEG_WORKGROUPS_PER_CU = 1.  The scans are fastest where B S reaches the number of CUs and lose beyond it: at 2^16,
+//     B = 64: S = 1 / 2 / 4 / 8 / 64 -> 4.51 / 2.75 / 1.79 / 1.84 / 2.64 ms; B = 8: fastest at S = 32 (0.53 ms, 4.33 at S = 1).
+//     So: S = 1 when B alone gives every CU a workgroup, else the smallest power of two with B S >= CUs.
+//   * SEG_MIN_ROWS = 256: a segment keeps a row for every lane of its workgroup.  At B = 1 the time stops falling there —
+//     2^13: 0.284 ms at S = 32 (256 rows), 0.287 / 0.286 / 0.308 at 64 / 128 / 256; 2^14: 0.291 at S = 64, 0.310 at 256 — and
+//     shorter segments only add idle lanes to the three launches.
+//   * SEG_MIN_LOG_N = 13 is not a measurement: up to 2^12 rows the launches are what the benchmark and the suite's fixtures have
+//     pinned, and they stay one workgroup per proof (the table has 0.15 ms of 2.0 to gain at 2^12, B <= 8).
+// With these the rule's choice beats S = 1 in every measured cell from 2^13 up, by more than the spread of five runs.
+#define SEG_WORKGROUPS_PER_CU 1
+#define SEG_MIN_ROWS 256
+#define SEG_MIN_LOG_N 13
+unsigned prover_plan_segments(unsigned cus, unsigned log_n, size_t B) {
+    if (log_n < SEG_MIN_LOG_N) return 1;
+    const size_t n = (size_t)1 << log_n, want = (size_t)SEG_WORKGROUPS_PER_CU * (cus ? cus : 1);
+    unsigned S = 1;
+    while ((size_t)S * B < want && S < SEG_THREADS && n / (2 * S) >= SEG_MIN_ROWS) S *= 2;
+    return S;
+}
+
+static unsigned device_cus(int device) {
+    static int cus[16] = {0};
+    int& n_cu = cus[device & 15];
+    if (!n_cu) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+        else {
+            (void)hipGetLastError();
+            n_cu = 256;
+        }
+    }
+    return (unsigned)n_cu;
+}
+
+// S of a prover's batch: PLONK_PROVER_SEGMENTS_LOG2 where it was set, the automatic rule otherwise
+static unsigned prover_segments(const plonk_prover* p, size_t B) {
+    return p->seg_forced ? 1u << (p->seg_forced - 1) : prover_plan_segments(device_cus(p->ctx->device), p->log_n, B);
+}
+
+// the segmented grand product: seg = 2 B S + B elements of scratch (numerator carries, denominator carries, the inversions)
+static int launch_grand_product_segmented(hipStream_t s, const GrandProductIn& gp, const Fr* roots, const ProofState* st,
+                                          const RoundChallenges& direct, size_t n, size_t B, unsigned S, Fr* z_out, uint32_t* closes,
+                                          Fr* num, Fr* den, Fr* seg) {
+    Fr *seg_n = seg, *seg_d = seg + B * S, *tot_inv = seg + 2 * B * S;
+    PLONK_LAUNCH(gp_seg_factors_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, gp, roots, st, direct, n, num, den, seg_n, seg_d);
+    PLONK_LAUNCH(gp_seg_carries_kernel, dim3((unsigned)B), dim3(SEG_THREADS), 0, s, S, seg_n, seg_d, tot_inv, closes);
+    PLONK_LAUNCH(gp_seg_apply_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, n, (const Fr*)seg_n, (const Fr*)seg_d,
+                 (const Fr*)tot_inv, (const Fr*)num, den, z_out);
+    return PLONK_OK;
+}
+
 static void free_batch(plonk_prover* p) {
+    dev_free_all({(void**)&p->seg});
+    p->seg_cap = 0;
     dev_free_all({(void**)&p->wit_lag, (void**)&p->z_lag, (void**)&p->coef, (void**)&p->big, (void**)&p->quot, (void**)&p->num, (void**)&p->closes,
                   (void**)&p->wz, (void**)&p->commit_xy, (void**)&p->commit_flags, (void**)&p->state, (void**)&p->pub, (void**)&p->lin_w,
                   (void**)&p->vars});
@@ -538,10 +871,21 @@ static void free_batch(plonk_prover* p) {
     p->cap_b = 0;
 }
 
-static int ensure_batch(plonk_prover* p, size_t B) {
-    if (B <= p->cap_b) return PLONK_OK;
+// the carries and partial sums of the segmented scans: 7 B S elements (the evaluations' seven partial sums per segment; the grand
+// product takes 2 B S + B of them, the two divisions 2 B S), none while S = 1
+static int ensure_segments(plonk_prover* p, size_t B) {
+    const unsigned S = prover_segments(p, B);
+    const size_t need = S > 1 ? (size_t)NEVAL * B * S + B : 0;
+    if (need <= p->seg_cap) return PLONK_OK;
     PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
-    free_batch(p);
+    dev_free_all({(void**)&p->seg});
+    p->seg_cap = 0;
+    PLONK_TRY(dev_alloc((void**)&p->seg, need * sizeof(Fr)));
+    p->seg_cap = need;
+    return PLONK_OK;
+}
+
+static int alloc_batch(plonk_prover* p, size_t B) {
     const size_t n = p->n, e = sizeof(Fr);
     PLONK_TRY(dev_alloc((void**)&p->wit_lag, 4 * B * n * e));
     PLONK_TRY(dev_alloc((void**)&p->z_lag, B * n * e));
@@ -556,8 +900,22 @@ static int ensure_batch(plonk_prover* p, size_t B) {
     PLONK_TRY(dev_alloc((void**)&p->state, B * sizeof(ProofState)));
     PLONK_TRY(dev_alloc((void**)&p->pub, (B * p->n_public + 1) * e));
     PLONK_TRY(dev_alloc((void**)&p->lin_w, B * sizeof(LinWeights)));
-    p->cap_b = B;
     return PLONK_OK;
+}
+
+static int ensure_batch(plonk_prover* p, size_t B) {
+    if (B <= p->cap_b) return ensure_segments(p, B);
+    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
+    free_batch(p);
+    const int rc = alloc_batch(p, B);
+    if (rc != PLONK_OK) {  // 32 n-vectors of 32 bytes per proof: 4 + 1 + 5 + 15 + 4 + 1 + 2
+        free_batch(p);
+        if (rc == PLONK_ERR_NOMEM)
+            plonk_set_error("a batch of %zu proofs of group_order %zu needs %zu bytes of device memory", B, p->n, 32 * B * p->n * sizeof(Fr));
+        return rc;
+    }
+    p->cap_b = B;
+    return ensure_segments(p, B);
 }
 
 static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32, size_t n_public);
@@ -570,7 +928,7 @@ int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const ui
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(log_n >= 1 && log_n + 2 <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "group_order 2^%u out of range", log_n);
     const size_t n = (size_t)1 << log_n;
-    PLONK_REQUIRE(n <= 4096, PLONK_ERR_ARG, "the batched prover supports group_order <= 4096 (got %zu)", n);
+    PLONK_REQUIRE(log_n <= PROVER_MAX_LOG_N, PLONK_ERR_ARG, "the batched prover supports group_order <= %u (got %zu)", 1u << PROVER_MAX_LOG_N, n);
     PLONK_REQUIRE(srs->n_points >= n, PLONK_ERR_ARG, "SRS has %zu powers, group_order is %zu", srs->n_points, n);
     PLONK_REQUIRE(n_public <= n, PLONK_ERR_ARG, "more public inputs than rows");
     plonk_prover* p = new plonk_prover();
@@ -659,8 +1017,12 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
 extern "C" {
 
 int plonk_prover_set_options(plonk_prover* p, unsigned flags) {
-    PLONK_REQUIRE(p && !(flags & ~PLONK_PROVER_LAGRANGE_COMMITS), PLONK_ERR_ARG, "unknown prover option bits %#x", flags);
+    PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK)), PLONK_ERR_ARG, "unknown prover option bits %#x", flags);
     PLONK_ENTER(p->ctx);
+    const unsigned seg = (flags & PLONK_PROVER_SEGMENTS_MASK) >> 8;  // k + 1, 0 = automatic
+    PLONK_REQUIRE(seg <= 9 && (!seg || (p->n >> (seg - 1)) >= 16), PLONK_ERR_ARG,
+                  "2^%u segments: at most 256, of at least 16 rows each (group_order %zu)", seg ? seg - 1 : 0, p->n);
+    p->seg_forced = seg;
     p->lag_srs = nullptr;
     if (flags & PLONK_PROVER_LAGRANGE_COMMITS) PLONK_TRY(msm_lagrange_srs(p->ctx, p->srs, p->log_n, &p->lag_srs));
     return PLONK_OK;
@@ -797,6 +1159,9 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     hipStream_t s = ctx->stream;
     Fq* cxy = p->commit_xy;
     uint8_t* cfl = p->commit_flags;
+    PLONK_REQUIRE(B <= 65535, PLONK_ERR_ARG, "batch %zu exceeds 65535 (the proofs are a grid's second dimension)", B);
+    PLONK_TRY(ensure_segments(p, B));  // (the options may have changed since the upload)
+    const unsigned S = prover_segments(p, B);  // 1: the one-workgroup scans
 
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 0, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
@@ -822,8 +1187,15 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
         gp.abc[k] = p->wit_lag + (size_t)k * B * n;
         gp.sig[k] = p->fixed_lag + (FX_S1 + k) * n;
     }
-    PLONK_LAUNCH(grand_product_kernel, dim3((unsigned)B), dim3(GP_THREADS), 0, s, gp, p->roots, (const ProofState*)p->state,
-                 RoundChallenges{}, n, p->z_lag, p->closes, p->num, p->wz);  // num / wz: scratch until round 5
+    // (the three scan families are instrumented for plonk_profile_read: tools/prover_scale.py)
+    PLONK_TRY(prof_begin(ctx, "prover_grand_product", 11.0 * 32.0 * (double)n * (double)B));
+    if (S > 1)
+        PLONK_TRY(launch_grand_product_segmented(s, gp, p->roots, (const ProofState*)p->state, RoundChallenges{}, n, B, S, p->z_lag, p->closes,
+                                                 p->num, p->wz, p->seg));
+    else
+        PLONK_LAUNCH(grand_product_kernel, dim3((unsigned)B), dim3(GP_THREADS), 0, s, gp, p->roots, (const ProofState*)p->state,
+                     RoundChallenges{}, n, p->z_lag, p->closes, p->num, p->wz);  // num / wz: scratch until round 5
+    PLONK_TRY(prof_end(ctx));
     PLONK_TRY(ntt_run(ctx, p->z_lag, p->coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
     if (p->lag_srs) PLONK_TRY(msm_run_device(ctx, p->lag_srs, p->z_lag, n, B, n, cxy + 2 * 3 * B, cfl + 3 * B));
     else PLONK_TRY(msm_run_device(ctx, p->srs, p->coef + 4 * B * n, n, B, n, cxy + 2 * 3 * B, cfl + 3 * B));
@@ -863,8 +1235,16 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_TRY(msm_run_device(ctx, p->srs, p->quot, n, 3 * B, n4, cxy + 2 * 4 * B, cfl + 4 * B, B, n));
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 3, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 4: evaluations                                                  prover.py:228-239
-    PLONK_LAUNCH(eval_kernel, dim3((unsigned)B), dim3(EV_THREADS), 0, s, (const Fr*)p->coef, (const Fr*)p->fixed_coef, p->w,
-                 p->state, n, B);
+    PLONK_TRY(prof_begin(ctx, "prover_evaluations", 7.0 * 32.0 * (double)n * (double)B));
+    if (S > 1) {
+        PLONK_LAUNCH(eval_seg_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, (const Fr*)p->coef, (const Fr*)p->fixed_coef, p->w,
+                     (const ProofState*)p->state, n, B, p->seg);
+        PLONK_LAUNCH(eval_seg_finish_kernel, dim3((unsigned)B), dim3(SEG_THREADS), 0, s, (const Fr*)p->seg, S, p->state);
+    } else {
+        PLONK_LAUNCH(eval_kernel, dim3((unsigned)B), dim3(EV_THREADS), 0, s, (const Fr*)p->coef, (const Fr*)p->fixed_coef, p->w,
+                     p->state, n, B);
+    }
+    PLONK_TRY(prof_end(ctx));
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 4, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 5: opening polynomials in coefficient form, commit              prover.py:241-306
     unsigned gx = (unsigned)((n + 255) / 256);
@@ -872,10 +1252,20 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_LAUNCH(linearisation_weights_kernel, dim3(tb), dim3(64), 0, s, (const ProofState*)p->state, log_n, p->n_inv, B, lw);
     PLONK_LAUNCH(linearisation_kernel, dim3(gx, (unsigned)B), dim3(256), 0, s, (const Fr*)p->coef,
                  (const Fr*)p->fixed_coef, (const Fr*)p->quot, (const LinWeights*)lw, log_n, B, p->num);
-    PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)p->num, n, 0, p->w,
-                 (const ProofState*)p->state, n, p->wz);
-    PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)(p->coef + 4 * B * n), n, 1,
-                 p->w, (const ProofState*)p->state, n, p->wz + B * n);
+    PLONK_TRY(prof_begin(ctx, "prover_divisions", 2.0 * 3.0 * 32.0 * (double)n * (double)B));
+    if (S > 1) {  // both openings share the launches (blockIdx.z)
+        const DivideIn dv = {{p->num, p->coef + 4 * B * n}, {p->wz, p->wz + B * n}};
+        PLONK_LAUNCH(divide_seg_horner_kernel, dim3(S, (unsigned)B, 2), dim3(SEG_THREADS), 0, s, dv, p->w, (const ProofState*)p->state, n, p->seg);
+        PLONK_LAUNCH(divide_seg_carries_kernel, dim3((unsigned)B, 1, 2), dim3(SEG_THREADS), 0, s, S, p->w, (const ProofState*)p->state, n, p->seg);
+        PLONK_LAUNCH(divide_seg_apply_kernel, dim3(S, (unsigned)B, 2), dim3(SEG_THREADS), 0, s, dv, p->w, (const ProofState*)p->state, n,
+                     (const Fr*)p->seg);
+    } else {
+        PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)p->num, n, 0, p->w,
+                     (const ProofState*)p->state, n, p->wz);
+        PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)(p->coef + 4 * B * n), n, 1,
+                     p->w, (const ProofState*)p->state, n, p->wz + B * n);
+    }
+    PLONK_TRY(prof_end(ctx));
     PLONK_TRY(msm_run_device(ctx, p->srs, p->wz, n, 2 * B, n, cxy + 2 * 7 * B, cfl + 7 * B));
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
@@ -920,6 +1310,13 @@ int plonk_prover_challenges(plonk_prover* p, size_t b, uint8_t out_le32[6 * 32])
     return PLONK_OK;
 }
 
+// DIAGNOSTICS: the automatic number of segments for `batch` proofs of 2^log_n rows on ctx's device
+int plonk_prover_plan_segments(plonk_ctx* ctx, unsigned log_n, size_t batch, unsigned* out_segments) {
+    PLONK_REQUIRE(ctx && out_segments && batch && log_n >= 1 && log_n <= PROVER_MAX_LOG_N, PLONK_ERR_ARG, "bad argument");
+    *out_segments = prover_plan_segments(device_cus(ctx->device), log_n, batch);
+    return PLONK_OK;
+}
+
 }  // extern "C"
 
 // ---- the fused round kernels on their own: what Prover.round_2 / round_3 of the reference-shaped API call
@@ -937,7 +1334,8 @@ int plonk_fr_grand_product(plonk_ctx* ctx, const void* d_a, const void* d_b, con
     const Fr* roots;
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &roots));
     void* scratch;
-    PLONK_TRY(ctx_scratch(ctx, 2, (2 * n + 2) * sizeof(Fr), &scratch));  // num, den, and the closes flag
+    const unsigned S = prover_plan_segments(device_cus(ctx->device), log_n, 1);
+    PLONK_TRY(ctx_scratch(ctx, 2, (2 * n + 2 + 2 * S + 1) * sizeof(Fr), &scratch));  // num, den, the closes flag, the segments' carries
     Fr* num = (Fr*)scratch;
     uint32_t* closes = reinterpret_cast<uint32_t*>(num + 2 * n);
     GrandProductIn gp = {{(const Fr*)d_a, (const Fr*)d_b, (const Fr*)d_c}, {(const Fr*)d_s1, (const Fr*)d_s2, (const Fr*)d_s3}};
@@ -945,8 +1343,11 @@ int plonk_fr_grand_product(plonk_ctx* ctx, const void* d_a, const void* d_b, con
     ch.beta = fr_from_le32(beta_le32);
     ch.gamma = fr_from_le32(gamma_le32);
     ch.alpha = fp_zero<FrParams>();
-    PLONK_LAUNCH(grand_product_kernel, dim3(1), dim3(GP_THREADS), 0, ctx->stream, gp, roots, (const ProofState*)nullptr, ch, n,
-                 (Fr*)d_z_out, closes, num, num + n);
+    if (S > 1)
+        PLONK_TRY(launch_grand_product_segmented(ctx->stream, gp, roots, nullptr, ch, n, 1, S, (Fr*)d_z_out, closes, num, num + n, num + 2 * n + 2));
+    else
+        PLONK_LAUNCH(grand_product_kernel, dim3(1), dim3(GP_THREADS), 0, ctx->stream, gp, roots, (const ProofState*)nullptr, ch, n,
+                     (Fr*)d_z_out, closes, num, num + n);
     PLONK_CHECK_HIP(hipGetLastError());
     uint32_t c = 0;
     PLONK_CHECK_HIP(hipMemcpyAsync(&c, closes, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
