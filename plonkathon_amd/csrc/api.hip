@@ -106,6 +106,21 @@ __global__ void fq_rescale_kernel(Fq* data, size_t n, unsigned doublings) {
     }
 }
 
+// compute units of a device, asked once per device; 256 (an MI355X) where the runtime does not say
+unsigned device_cus(int device) {
+    static int cus[16] = {0};
+    int& n_cu = cus[device & 15];
+    if (!n_cu) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+        else {
+            (void)hipGetLastError();
+            n_cu = 256;
+        }
+    }
+    return (unsigned)n_cu;
+}
+
 extern "C" {
 
 const char* plonk_last_error(void) { return g_err; }

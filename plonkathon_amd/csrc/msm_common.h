@@ -151,17 +151,7 @@ static void msm_recode_constant(unsigned c, unsigned W, MsmRecode* rc) {
 // bucket method 5.59 -> 5.14 ms per call; the prover's own launch shapes gain under 1 % on either method.
 static unsigned msm_round_aware_groups(int device, size_t M, unsigned g0, unsigned g_max, double overhead) {
     if (g0 >= g_max) return g0;
-    static int cus[16] = {0};
-    int& n_cu = cus[device & 15];
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        else {
-            (void)hipGetLastError();
-            n_cu = 256;
-        }
-    }
-    const double slots = 4.0 * (double)n_cu;
+    const double slots = 4.0 * (double)device_cus(device);
     auto cost = [&](unsigned G) {
         const double wgs = (double)M * G;
         double rounds = wgs / slots;

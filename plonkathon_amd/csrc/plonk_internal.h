@@ -205,6 +205,7 @@ int k_fr_count_diff(plonk_ctx*, const Fr* a, const Fr* b_or_null, size_t n, unsi
 Fr fr_from_le32(const uint8_t* b);                 // canonical little-endian bytes -> Montgomery form (host)
 bool le32_below_modulus(const uint8_t* b, bool fq);
 int get_power_table(plonk_ctx*, const Fr& base, const Fr& first, size_t n, const Fr** out);  // first * base^i, cached per context
+unsigned device_cus(int device);                   // compute units, cached per device (the MSM's launch rounds, the prover's segments)
 // ntt.hip
 Fr host_root_of_unity(unsigned log_n, bool inverse);
 // fan (optional): every batch entry is transformed `count` times — copy f reads in + f in_stride, writes out + f out_stride

@@ -14,6 +14,10 @@ struct ProofState {
     uint32_t pad_[3];
 };
 
+// The challenges of rounds 2 and 3 where a kernel runs outside a proof's transcript (st == null: plonk_fr_grand_product,
+// plonk_fr_quotient); the lock-step prover's kernels read them from the ProofStates and pass an empty one.
+struct RoundChallenges { Fr beta, gamma, alpha; };
+
 // the prover's status byte (pack_status_kernel; 0 = the proof is good)
 #define PROVER_ST_IDENTITY 1u   // a commitment was the identity
 #define PROVER_ST_Z_OPEN 2u     // Z does not close to 1: the witness breaks the copy constraints (prover.py:132)
@@ -73,8 +77,8 @@ struct plonk_prover {
     uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
     Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
     struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
-    // the segmented scans (prover.hip): carries and partial sums of the S segments of every proof, none while S = 1
-    Fr* seg;                   // [7 B S + B]
+    // the segmented scans (prover_scans.h): carries and partial sums of the S segments of every proof, none while S = 1
+    Fr* seg;                   // [scan_scratch_elems(B, S)]
     size_t seg_cap;            // elements
     unsigned seg_forced;       // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
     // wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device

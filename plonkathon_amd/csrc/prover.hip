@@ -20,6 +20,7 @@
 
 #include "prover.h"
 #include "g1_codec.h"
+#include "prover_scans.h"  // rounds 2, 4 and 5: the grand product, the evaluations, the divisions — kernels and launchers
 
 // ------------------------------------------------------------------------------------------------
 // witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
@@ -132,84 +133,6 @@ __global__ void __launch_bounds__(2 * TC_LANES) transcript_kernel(int round, Pro
 }
 
 // ------------------------------------------------------------------------------------------------
-// Round 2 (prover.py:121-152): the permutation grand product, one workgroup per proof.
-//   num_i = (A_i + b w^i + g)(B_i + 2 b w^i + g)(C_i + 3 b w^i + g)
-//   den_i = (A_i + b S1_i + g)(B_i + b S2_i + g)(C_i + b S3_i + g)
-//   Z_0 = 1, Z_{i+1} = Z_i num_i / den_i
-// With PN_i = prod_{j<i} num_j and SD_i = prod_{j>=i} den_j:  Z_i = PN_i * SD_i / prod_j den_j, so the
-// whole column costs two block scans and ONE field inversion.  A zero denominator factor is skipped
-// in the scans and zeroes the ratio it belongs to (py_ecc: x / 0 == 0).
-#define GP_THREADS 256
-// Inputs by pointer: proof b's columns at abc[k] + b n, the permutation polynomials sig[k] shared.  The challenges come
-// from the proofs' transcript states (st, the lock-step prover) or, st == null, from `direct` (plonk_fr_grand_product).
-struct RoundChallenges { Fr beta, gamma, alpha; };
-struct GrandProductIn { const Fr* abc[3]; const Fr* sig[3]; };
-__global__ void __launch_bounds__(GP_THREADS) grand_product_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
-                                                                   RoundChallenges direct, size_t n, Fr* z_out,
-                                                                   uint32_t* closes, Fr* num_buf, Fr* den_buf) {
-    __shared__ Fr sc_n[GP_THREADS], sc_d[GP_THREADS];
-    __shared__ Fr tot_inv;
-    const size_t b = blockIdx.x;
-    const unsigned tid = threadIdx.x;
-    const Fr beta = st ? st[b].beta : direct.beta, gamma = st ? st[b].gamma : direct.gamma;
-    const Fr *A = in.abc[0] + b * n, *Bv = in.abc[1] + b * n, *C = in.abc[2] + b * n;
-    const Fr *S1 = in.sig[0], *S2 = in.sig[1], *S3 = in.sig[2];
-    Fr *NUM = num_buf + b * n, *DEN = den_buf + b * n;  // this proof's factors; a lane only ever touches its own chunk
-    const size_t per = (n + GP_THREADS - 1) / GP_THREADS;
-    const size_t lo = tid * per, hi = (lo + per < n) ? lo + per : n;
-    const Fr one = fp_one<FrParams>();
-
-    // pass 1: the factors, once; per-lane products
-    Fr pn = one, pd = one;
-    for (size_t i = lo; i < hi; i++) {
-        Fr a = fp_load(A + i), bb = fp_load(Bv + i), c = fp_load(C + i);
-        Fr bw = fp_mul(beta, fp_load(roots + i));
-        Fr ag = fp_add(a, gamma), bg = fp_add(bb, gamma), cg = fp_add(c, gamma);
-        Fr num = fp_mul(fp_mul(fp_add(ag, bw), fp_add(bg, fp_dbl(bw))), fp_add(cg, fp_mul3(bw)));
-        Fr den = fp_mul(fp_mul(fp_add(ag, fp_mul(beta, fp_load(S1 + i))), fp_add(bg, fp_mul(beta, fp_load(S2 + i)))),
-                        fp_add(cg, fp_mul(beta, fp_load(S3 + i))));
-        if (fp_is_zero(den)) {  // ratio num/0 == 0 (py_ecc): the factor leaves the denominator products
-            num = fp_zero<FrParams>();
-            den = one;
-        }
-        fp_store(NUM + i, num);
-        fp_store(DEN + i, den);
-        pd = fp_mul(pd, den);
-        pn = fp_mul(pn, num);
-    }
-    sc_n[tid] = pn;
-    sc_d[tid] = pd;
-    __syncthreads();
-    // inclusive prefix scan of sc_n (Hillis-Steele), inclusive suffix scan of sc_d
-    for (unsigned off = 1; off < GP_THREADS; off <<= 1) {
-        Fr vn = sc_n[tid], vd = sc_d[tid];
-        if (tid >= off) vn = fp_mul(vn, sc_n[tid - off]);
-        if (tid + off < GP_THREADS) vd = fp_mul(vd, sc_d[tid + off]);
-        __syncthreads();
-        sc_n[tid] = vn;
-        sc_d[tid] = vd;
-        __syncthreads();
-    }
-    if (tid == 0) tot_inv = fp_inv(sc_d[0]);  // product of all non-zero denominators
-    __syncthreads();
-    Fr run_n = tid ? sc_n[tid - 1] : one;                       // prod of num before this lane's chunk
-    Fr after_d = (tid + 1 < GP_THREADS) ? sc_d[tid + 1] : one;  // prod of den after this lane's chunk
-    const Fr tinv = tot_inv;
-    // pass 2 (backwards): DEN[k] <- prod_{j >= k} den_j
-    for (size_t k = hi; k-- > lo;) {
-        after_d = fp_mul(after_d, fp_load(DEN + k));
-        fp_store(DEN + k, after_d);
-    }
-    // pass 3: Z_i = PN_i * SD_i * tot_inv
-    for (size_t i = lo; i < hi; i++) {
-        fp_store(z_out + b * n + i, fp_mul(fp_mul(run_n, fp_load(DEN + i)), tinv));
-        run_n = fp_mul(run_n, fp_load(NUM + i));
-    }
-    // prover.py:132 `assert Z_values.pop() == 1`: the full product of ratios must close to one
-    if (tid == GP_THREADS - 1) closes[b] = fp_eq(fp_mul(run_n, tinv), fp_one<FrParams>()) ? 1u : 0u;
-}
-
-// ------------------------------------------------------------------------------------------------
 // Round 3 (prover.py:188-203): quotient evaluations on the coset points, fully fused.
 //   wit = A, B, C, PI, Z on the points, proof b at + b n4; fixed = QM, QL, QR, QO, QC, S1, S2, S3 (FX_* order), l0, xs: [n4].
 //   Challenges from the transcript states (st) or, st == null, from `direct` (plonk_fr_quotient).
@@ -311,50 +234,6 @@ __global__ void gate_check_kernel(const Fr* abc, const Fr* pub, size_t l, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Round 4 (prover.py:228-239): evaluate coefficient forms at zeta (and Z at zeta*w), one workgroup
-// per proof: lane t Horner-evaluates its chunk of each polynomial, scales by x^(chunk start) and
-// the workgroup tree-reduces.  polys: Ac, Bc, Cc, S1c, S2c at zeta; Zc at zeta*w; PIc at zeta.
-#define EV_THREADS 256
-__global__ void __launch_bounds__(EV_THREADS) eval_kernel(const Fr* coef, const Fr* fixed_coef, Fr w, ProofState* st,
-                                                          size_t n, size_t B) {
-    __shared__ Fr red[NEVAL][EV_THREADS];
-    const size_t b = blockIdx.x;
-    const unsigned tid = threadIdx.x;
-    const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    const Fr* polys[NEVAL] = {coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
-                              fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (4 * B + b) * n,
-                              coef + (3 * B + b) * n};
-    const size_t per = (n + EV_THREADS - 1) / EV_THREADS;
-    const size_t lo = tid * per, hi = (lo + per < n) ? lo + per : n;
-    // x^(chunk start) once per evaluation point, not once per polynomial
-    const Fr shift_z = fp_pow_u64(zeta, (uint64_t)lo), shift_zw = fp_pow_u64(zeta_w, (uint64_t)lo);
-    // Horner on lazy limbs (round 4), the seven chains side by side: acc x is normalised in (-m, 2m), plus a coefficient it is a
-    // sum of two — a valid multiplicand as it stands; the evaluation points sit in scalar registers
-    typedef FpL<FrParams> L;
-    const L zl = fpl_from_fp_uniform(zeta), zwl = fpl_from_fp_uniform(zeta_w);
-    L acc[NEVAL];
-    wave_for<NEVAL>([&](auto P_) { acc[decltype(P_)::value] = fpl_zero<FrParams>(); });
-#pragma unroll 1
-    for (size_t i = hi; i-- > lo;)
-        wave_for<NEVAL>([&](auto P_) {
-            constexpr unsigned p = decltype(P_)::value;
-            acc[p] = fpl_add(fpl_mul(acc[p], p == 5 ? zwl : zl), fpl_from_fp(fp_load(polys[p] + i)));  // (-m, 3m), limbs < 2^30
-        });
-    const L sh_z = fpl_from_fp(shift_z), sh_zw = fpl_from_fp(shift_zw);
-    wave_for<NEVAL>([&](auto P_) {
-        constexpr unsigned p = decltype(P_)::value;
-        red[p][tid] = lo < hi ? fpl_pack_canonical(fpl_mul(acc[p], p == 5 ? sh_zw : sh_z)) : fp_zero<FrParams>();
-    });
-    __syncthreads();
-    for (unsigned s = EV_THREADS / 2; s > 0; s >>= 1) {  // the seven sums share the barriers
-        if (tid < s)
-            for (int p = 0; p < NEVAL; p++) red[p][tid] = fp_add(red[p][tid], red[p][tid + s]);
-        __syncthreads();
-    }
-    if (tid < NEVAL) st[b].evals[tid] = red[tid][0];
-}
-
-// ------------------------------------------------------------------------------------------------
 // Round 5 (prover.py:241-306) in coefficient form.  numerator of W_z:
 //   R + v(A - a) + v^2(B - b) + v^3(C - c) + v^4(S1 - s1) + v^5(S2 - s2)
 // is a linear combination of 15 coefficient vectors; the constants only change the remainder of the
@@ -447,319 +326,6 @@ __global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, c
     }
 }
 
-// q(X) = (p(X) - p(x0)) / (X - x0): q_{n-1} = 0, q_{i-1} = p_i + x0 q_i.  One workgroup per proof;
-// lane t owns a chunk, the cross-chunk carries are a suffix scan under (a, m) o (b, m') = (a + m b, m m').
-#define DV_THREADS 256
-__global__ void __launch_bounds__(DV_THREADS) divide_linear_kernel(const Fr* p_in, size_t in_stride, int which,
-                                                                  Fr w, const ProofState* st, size_t n, Fr* q_out) {
-    __shared__ Fr sc[DV_THREADS];
-    const size_t b = blockIdx.x;
-    const unsigned tid = threadIdx.x;
-    Fr x0 = st[b].zeta;
-    if (which) x0 = fp_mul(x0, w);  // zeta * w for W_zw (prover.py:292-297)
-    const Fr* p = p_in + b * in_stride;
-    const size_t per = (n + DV_THREADS - 1) / DV_THREADS;
-    const size_t lo = tid * per, hi = (lo + per < n) ? lo + per : n;
-    // h_t = sum_{i in chunk} p_i x0^(i - lo)
-    Fr h = fp_zero<FrParams>();
-    for (size_t i = hi; i-- > lo;) h = fp_add(fp_mul(h, x0), fp_load(p + i));
-    sc[tid] = h;
-    __syncthreads();
-    // suffix scan: after it, sc[t] = sum_{u >= t} h_u x0^((u - t) per)
-    Fr m = fp_pow_u64(x0, (uint64_t)per);
-    for (unsigned off = 1; off < DV_THREADS; off <<= 1) {
-        Fr vv = sc[tid];
-        if (tid + off < DV_THREADS) vv = fp_add(vv, fp_mul(m, sc[tid + off]));
-        __syncthreads();
-        sc[tid] = vv;
-        m = fp_sqr(m);
-        __syncthreads();
-    }
-    // carry into this chunk = value of q at index (hi - 1), i.e. contribution of all higher chunks:
-    // q_{hi-1} = sum_{j >= hi} p_j x0^(j - hi) = sc[t + 1]
-    Fr q = (tid + 1 < DV_THREADS) ? sc[tid + 1] : fp_zero<FrParams>();
-    for (size_t i = hi; i-- > lo;) {
-        fp_store(q_out + b * n + i, q);          // q_i
-        q = fp_add(fp_load(p + i), fp_mul(x0, q));  // q_{i-1} = p_i + x0 q_i
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Segmented forms of the three per-proof scans (grand product, evaluations, division by X - x0) for batches too small to fill the
-// chip with one workgroup per proof.  A proof's n rows are cut into S equal segments (S a power of two, 2 <= S <= 256,
-// n / S >= 16) and every scan becomes three launches, or two, on the prover's stream: per-segment work on a grid of (S, B)
-// workgroups, a small per-proof launch that turns the S segment totals into carries, and a second (S, B) launch that applies
-// them.  The launches are ordered by the stream alone: no workgroup ever waits for another inside a kernel.  Everything is a
-// canonical residue of an associative operation, so the results are the bits the one-workgroup kernels above (S = 1) give.
-// n and S are powers of two, so a segment's L = n / S rows fall on its 256 lanes as `per` = max(L / 256, 1) rows each: lanes
-// below min(L, 256) hold exactly `per` rows, the others none, and an empty lane carries the scan's neutral element.
-#define SEG_THREADS 256
-struct SegRange { size_t lo, hi, per; };
-PLONK_DEV SegRange seg_lane_range(size_t n, unsigned S, unsigned seg, unsigned tid) {
-    const size_t L = n / S, per = (L + SEG_THREADS - 1) / SEG_THREADS, s_lo = (size_t)seg * L, s_hi = s_lo + L;
-    SegRange r;
-    r.per = per;
-    r.lo = s_lo + (size_t)tid * per < s_hi ? s_lo + (size_t)tid * per : s_hi;
-    r.hi = r.lo + per < s_hi ? r.lo + per : s_hi;
-    return r;
-}
-
-// Grand product, launch 1 of 3, grid (S, B): the factors of the segment's rows into num_buf / den_buf (grand_product_kernel's
-// pass 1), and the segment's two products into seg_n / seg_d [B][S].
-__global__ void __launch_bounds__(SEG_THREADS) gp_seg_factors_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
-                                                                     RoundChallenges direct, size_t n, Fr* num_buf, Fr* den_buf,
-                                                                     Fr* seg_n, Fr* seg_d) {
-    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
-    const size_t b = blockIdx.y;
-    const unsigned tid = threadIdx.x, S = gridDim.x;
-    const Fr beta = st ? st[b].beta : direct.beta, gamma = st ? st[b].gamma : direct.gamma;
-    const Fr *A = in.abc[0] + b * n, *Bv = in.abc[1] + b * n, *C = in.abc[2] + b * n;
-    const Fr *S1 = in.sig[0], *S2 = in.sig[1], *S3 = in.sig[2];
-    Fr *NUM = num_buf + b * n, *DEN = den_buf + b * n;
-    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
-    const Fr one = fp_one<FrParams>();
-    Fr pn = one, pd = one;
-    for (size_t i = r.lo; i < r.hi; i++) {
-        Fr a = fp_load(A + i), bb = fp_load(Bv + i), c = fp_load(C + i);
-        Fr bw = fp_mul(beta, fp_load(roots + i));
-        Fr ag = fp_add(a, gamma), bg = fp_add(bb, gamma), cg = fp_add(c, gamma);
-        Fr num = fp_mul(fp_mul(fp_add(ag, bw), fp_add(bg, fp_dbl(bw))), fp_add(cg, fp_mul3(bw)));
-        Fr den = fp_mul(fp_mul(fp_add(ag, fp_mul(beta, fp_load(S1 + i))), fp_add(bg, fp_mul(beta, fp_load(S2 + i)))),
-                        fp_add(cg, fp_mul(beta, fp_load(S3 + i))));
-        if (fp_is_zero(den)) {  // ratio num/0 == 0 (py_ecc): the factor leaves the denominator products
-            num = fp_zero<FrParams>();
-            den = one;
-        }
-        fp_store(NUM + i, num);
-        fp_store(DEN + i, den);
-        pd = fp_mul(pd, den);
-        pn = fp_mul(pn, num);
-    }
-    sc_n[tid] = pn;
-    sc_d[tid] = pd;
-    __syncthreads();
-    for (unsigned s = SEG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            sc_n[tid] = fp_mul(sc_n[tid], sc_n[tid + s]);
-            sc_d[tid] = fp_mul(sc_d[tid], sc_d[tid + s]);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        fp_store(seg_n + b * S + blockIdx.x, sc_n[0]);
-        fp_store(seg_d + b * S + blockIdx.x, sc_d[0]);
-    }
-}
-
-// Launch 2 of 3, one workgroup per proof, lane s = segment s: seg_n[s] <- prod of the numerators BEFORE segment s, seg_d[s] <-
-// prod of the denominators AFTER it, tot_inv[b] = the proof's one inversion, closes[b].
-__global__ void __launch_bounds__(SEG_THREADS) gp_seg_carries_kernel(unsigned S, Fr* seg_n, Fr* seg_d, Fr* tot_inv, uint32_t* closes) {
-    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
-    const size_t b = blockIdx.x;
-    const unsigned tid = threadIdx.x;
-    const Fr one = fp_one<FrParams>();
-    sc_n[tid] = tid < S ? fp_load(seg_n + b * S + tid) : one;
-    sc_d[tid] = tid < S ? fp_load(seg_d + b * S + tid) : one;
-    __syncthreads();
-    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {  // inclusive prefix of sc_n, inclusive suffix of sc_d
-        Fr vn = sc_n[tid], vd = sc_d[tid];
-        if (tid >= off) vn = fp_mul(vn, sc_n[tid - off]);
-        if (tid + off < SEG_THREADS) vd = fp_mul(vd, sc_d[tid + off]);
-        __syncthreads();
-        sc_n[tid] = vn;
-        sc_d[tid] = vd;
-        __syncthreads();
-    }
-    if (tid < S) {
-        fp_store(seg_n + b * S + tid, tid ? sc_n[tid - 1] : one);
-        fp_store(seg_d + b * S + tid, tid + 1 < SEG_THREADS ? sc_d[tid + 1] : one);
-    }
-    if (tid == 0) {
-        const Fr tinv = fp_inv(sc_d[0]);  // product of all non-zero denominators
-        fp_store(tot_inv + b, tinv);
-        closes[b] = fp_eq(fp_mul(sc_n[SEG_THREADS - 1], tinv), one) ? 1u : 0u;  // prover.py:132
-    }
-}
-
-// Launch 3 of 3, grid (S, B): grand_product_kernel's passes 2 and 3 inside the segment, seeded with its carries.
-__global__ void __launch_bounds__(SEG_THREADS) gp_seg_apply_kernel(size_t n, const Fr* seg_n, const Fr* seg_d, const Fr* tot_inv,
-                                                                   const Fr* num_buf, Fr* den_buf, Fr* z_out) {
-    __shared__ Fr sc_n[SEG_THREADS], sc_d[SEG_THREADS];
-    const size_t b = blockIdx.y;
-    const unsigned tid = threadIdx.x, S = gridDim.x;
-    const Fr* NUM = num_buf + b * n;
-    Fr* DEN = den_buf + b * n;
-    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
-    const Fr one = fp_one<FrParams>();
-    Fr pn = one, pd = one;
-    for (size_t i = r.lo; i < r.hi; i++) {
-        pn = fp_mul(pn, fp_load(NUM + i));
-        pd = fp_mul(pd, fp_load(DEN + i));
-    }
-    sc_n[tid] = pn;
-    sc_d[tid] = pd;
-    __syncthreads();
-    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
-        Fr vn = sc_n[tid], vd = sc_d[tid];
-        if (tid >= off) vn = fp_mul(vn, sc_n[tid - off]);
-        if (tid + off < SEG_THREADS) vd = fp_mul(vd, sc_d[tid + off]);
-        __syncthreads();
-        sc_n[tid] = vn;
-        sc_d[tid] = vd;
-        __syncthreads();
-    }
-    Fr run_n = fp_load(seg_n + b * S + blockIdx.x), after_d = fp_load(seg_d + b * S + blockIdx.x);
-    if (tid) run_n = fp_mul(run_n, sc_n[tid - 1]);
-    if (tid + 1 < SEG_THREADS) after_d = fp_mul(after_d, sc_d[tid + 1]);
-    const Fr tinv = fp_load(tot_inv + b);
-    for (size_t k = r.hi; k-- > r.lo;) {  // DEN[k] <- prod_{j >= k} den_j
-        after_d = fp_mul(after_d, fp_load(DEN + k));
-        fp_store(DEN + k, after_d);
-    }
-    for (size_t i = r.lo; i < r.hi; i++) {  // Z_i = PN_i * SD_i * tot_inv
-        fp_store(z_out + b * n + i, fp_mul(fp_mul(run_n, fp_load(DEN + i)), tinv));
-        run_n = fp_mul(run_n, fp_load(NUM + i));
-    }
-}
-
-// Evaluations, launch 1 of 2, grid (S, B): eval_kernel's blocked Horner over the segment's rows, every lane's chains scaled by
-// x^(global chunk start); the segment's seven sums go to part[b][s][NEVAL].
-__global__ void __launch_bounds__(SEG_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, Fr w, const ProofState* st,
-                                                               size_t n, size_t B, Fr* part) {
-    __shared__ Fr red[NEVAL][SEG_THREADS];
-    const size_t b = blockIdx.y;
-    const unsigned tid = threadIdx.x, S = gridDim.x;
-    const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    const Fr* polys[NEVAL] = {coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
-                              fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (4 * B + b) * n,
-                              coef + (3 * B + b) * n};
-    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
-    const Fr shift_z = fp_pow_u64(zeta, (uint64_t)r.lo), shift_zw = fp_pow_u64(zeta_w, (uint64_t)r.lo);
-    typedef FpL<FrParams> L;
-    const L zl = fpl_from_fp_uniform(zeta), zwl = fpl_from_fp_uniform(zeta_w);
-    L acc[NEVAL];
-    wave_for<NEVAL>([&](auto P_) { acc[decltype(P_)::value] = fpl_zero<FrParams>(); });
-#pragma unroll 1
-    for (size_t i = r.hi; i-- > r.lo;)
-        wave_for<NEVAL>([&](auto P_) {
-            constexpr unsigned p = decltype(P_)::value;
-            acc[p] = fpl_add(fpl_mul(acc[p], p == 5 ? zwl : zl), fpl_from_fp(fp_load(polys[p] + i)));  // (-m, 3m), limbs < 2^30
-        });
-    const L sh_z = fpl_from_fp(shift_z), sh_zw = fpl_from_fp(shift_zw);
-    wave_for<NEVAL>([&](auto P_) {
-        constexpr unsigned p = decltype(P_)::value;
-        red[p][tid] = r.lo < r.hi ? fpl_pack_canonical(fpl_mul(acc[p], p == 5 ? sh_zw : sh_z)) : fp_zero<FrParams>();
-    });
-    __syncthreads();
-    for (unsigned s = SEG_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int p = 0; p < NEVAL; p++) red[p][tid] = fp_add(red[p][tid], red[p][tid + s]);
-        __syncthreads();
-    }
-    if (tid < NEVAL) fp_store(part + (b * S + blockIdx.x) * NEVAL + tid, red[tid][0]);
-}
-
-// Launch 2 of 2, one workgroup per proof: lane group p (32 lanes) adds the S partial sums of evaluation p into st[b].evals[p].
-__global__ void __launch_bounds__(SEG_THREADS) eval_seg_finish_kernel(const Fr* part, unsigned S, ProofState* st) {
-    __shared__ Fr red[SEG_THREADS];
-    const size_t b = blockIdx.x;
-    const unsigned tid = threadIdx.x, p = tid / 32, l = tid % 32;
-    Fr acc = fp_zero<FrParams>();
-    if (p < NEVAL)
-        for (unsigned s = l; s < S; s += 32) acc = fp_add(acc, fp_load(part + (b * S + s) * NEVAL + p));
-    red[tid] = acc;
-    __syncthreads();
-    for (unsigned s = 16; s > 0; s >>= 1) {
-        if (l < s) red[tid] = fp_add(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    if (l == 0 && p < NEVAL) st[b].evals[p] = red[tid];
-}
-
-// Division by X - x0, both openings at once: blockIdx.z = 0 divides p_in[0] by X - zeta, 1 divides p_in[1] by X - zeta w.
-struct DivideIn { const Fr* p_in[2]; Fr* q_out[2]; };
-// the lane's Horner value h = sum_{i in chunk} p_i x0^(i - lo)
-PLONK_DEV Fr divide_chunk_horner(const Fr* p, const SegRange& r, const Fr& x0) {
-    Fr h = fp_zero<FrParams>();
-    for (size_t i = r.hi; i-- > r.lo;) h = fp_add(fp_mul(h, x0), fp_load(p + i));
-    return h;
-}
-// Launch 1 of 3, grid (S, B, 2): the segment's Horner value H_s = sum_{i in segment} p_i x0^(i - segment start) into seg_h[z][b][s].
-__global__ void __launch_bounds__(SEG_THREADS) divide_seg_horner_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
-    __shared__ Fr sc[SEG_THREADS];
-    const size_t b = blockIdx.y, B = gridDim.y;
-    const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
-    Fr x0 = st[b].zeta;
-    if (z) x0 = fp_mul(x0, w);
-    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
-    sc[tid] = divide_chunk_horner(in.p_in[z] + b * n, r, x0);
-    __syncthreads();
-    Fr m = fp_pow_u64(x0, (uint64_t)r.per);  // x0^(per * off)
-    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
-        if ((tid & (2 * off - 1)) == 0) sc[tid] = fp_add(sc[tid], fp_mul(m, sc[tid + off]));
-        m = fp_sqr(m);
-        __syncthreads();
-    }
-    if (tid == 0) fp_store(seg_h + ((size_t)z * B + b) * S + blockIdx.x, sc[0]);
-}
-
-// Launch 2 of 3, grid (B, 1, 2), lane s = segment s: the suffix scan over segments under (a, m) o (b, m') = (a + m b, m m') with
-// m = x0^(n / S); seg_h[s] <- the carry entering segment s, q at the segment's last index = sum_{j >= segment end} p_j x0^(j - end).
-__global__ void __launch_bounds__(SEG_THREADS) divide_seg_carries_kernel(unsigned S, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
-    __shared__ Fr sc[SEG_THREADS];
-    const size_t b = blockIdx.x, B = gridDim.x;
-    const unsigned tid = threadIdx.x, z = blockIdx.z;
-    Fr x0 = st[b].zeta;
-    if (z) x0 = fp_mul(x0, w);
-    Fr* h = seg_h + ((size_t)z * B + b) * S;
-    sc[tid] = tid < S ? fp_load(h + tid) : fp_zero<FrParams>();
-    __syncthreads();
-    Fr m = fp_pow_u64(x0, (uint64_t)(n / S));
-    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
-        Fr vv = sc[tid];
-        if (tid + off < SEG_THREADS) vv = fp_add(vv, fp_mul(m, sc[tid + off]));
-        __syncthreads();
-        sc[tid] = vv;
-        m = fp_sqr(m);
-        __syncthreads();
-    }
-    if (tid < S) fp_store(h + tid, tid + 1 < SEG_THREADS ? sc[tid + 1] : fp_zero<FrParams>());
-}
-
-// Launch 3 of 3, grid (S, B, 2): divide_linear_kernel inside the segment; the segment's carry enters its last lane, as the value
-// one chunk above that lane's rows.
-__global__ void __launch_bounds__(SEG_THREADS) divide_seg_apply_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, const Fr* seg_h) {
-    __shared__ Fr sc[SEG_THREADS];
-    const size_t b = blockIdx.y, B = gridDim.y;
-    const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
-    Fr x0 = st[b].zeta;
-    if (z) x0 = fp_mul(x0, w);
-    const Fr* p = in.p_in[z] + b * n;
-    const SegRange r = seg_lane_range(n, S, blockIdx.x, tid);
-    const size_t L = n / S;
-    const unsigned last = (unsigned)(L < SEG_THREADS ? L : SEG_THREADS) - 1;  // the last lane that holds rows
-    const Fr carry = fp_load(seg_h + ((size_t)z * B + b) * S + blockIdx.x);
-    Fr m = fp_pow_u64(x0, (uint64_t)r.per);
-    Fr h = divide_chunk_horner(p, r, x0);
-    if (tid == last) h = fp_add(h, fp_mul(m, carry));
-    sc[tid] = h;
-    __syncthreads();
-    for (unsigned off = 1; off < SEG_THREADS; off <<= 1) {
-        Fr vv = sc[tid];
-        if (tid + off < SEG_THREADS) vv = fp_add(vv, fp_mul(m, sc[tid + off]));
-        __syncthreads();
-        sc[tid] = vv;
-        m = fp_sqr(m);
-        __syncthreads();
-    }
-    Fr q = tid < last ? sc[tid + 1] : carry;
-    Fr* out = in.q_out[z] + b * n;
-    for (size_t i = r.hi; i-- > r.lo;) {
-        fp_store(out + i, q);                       // q_i
-        q = fp_add(fp_load(p + i), fp_mul(x0, q));  // q_{i-1} = p_i + x0 q_i
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // pack results: [B] proof records (prover.h), plain or compressed
 __global__ void pack_proofs_kernel(const Fq* commit_xy, const ProofState* st, size_t B, uint8_t* out, int compressed) {
@@ -806,58 +372,9 @@ __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes,
 // ================================================================================================
 // host side
 
-// How many segments S the three per-proof scans are cut into for `B` proofs of 2^log_n rows on a device of `cus` compute units
-// (1: the one-workgroup kernels).  Measured on an MI355X, 256 CUs (profiles/prover_large.json, tools/prover_scale.py; the table
-// is in DESIGN.md 4.3), the three scans together, per plonk_prover_run:
-//   * SEG_WORKGROUPS_PER_CU = 1.  The scans are fastest where B S reaches the number of CUs and lose beyond it: at 2^16,
-//     B = 64: S = 1 / 2 / 4 / 8 / 64 -> 4.51 / 2.75 / 1.79 / 1.84 / 2.64 ms; B = 8: fastest at S = 32 (0.53 ms, 4.33 at S = 1).
-//     So: S = 1 when B alone gives every CU a workgroup, else the smallest power of two with B S >= CUs.
-//   * SEG_MIN_ROWS = 256: a segment keeps a row for every lane of its workgroup.  At B = 1 the time stops falling there —
-//     2^13: 0.284 ms at S = 32 (256 rows), 0.287 / 0.286 / 0.308 at 64 / 128 / 256; 2^14: 0.291 at S = 64, 0.310 at 256 — and
-//     shorter segments only add idle lanes to the three launches.
-//   * SEG_MIN_LOG_N = 13 is not a measurement: up to 2^12 rows the launches are what the benchmark and the suite's fixtures have
-//     pinned, and they stay one workgroup per proof (the table has 0.15 ms of 2.0 to gain at 2^12, B <= 8).
-// With these the rule's choice beats S = 1 in every measured cell from 2^13 up, by more than the spread of five runs.
-#define SEG_WORKGROUPS_PER_CU 1
-#define SEG_MIN_ROWS 256
-#define SEG_MIN_LOG_N 13
-unsigned prover_plan_segments(unsigned cus, unsigned log_n, size_t B) {
-    if (log_n < SEG_MIN_LOG_N) return 1;
-    const size_t n = (size_t)1 << log_n, want = (size_t)SEG_WORKGROUPS_PER_CU * (cus ? cus : 1);
-    unsigned S = 1;
-    while ((size_t)S * B < want && S < SEG_THREADS && n / (2 * S) >= SEG_MIN_ROWS) S *= 2;
-    return S;
-}
-
-static unsigned device_cus(int device) {
-    static int cus[16] = {0};
-    int& n_cu = cus[device & 15];
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        else {
-            (void)hipGetLastError();
-            n_cu = 256;
-        }
-    }
-    return (unsigned)n_cu;
-}
-
 // S of a prover's batch: PLONK_PROVER_SEGMENTS_LOG2 where it was set, the automatic rule otherwise
 static unsigned prover_segments(const plonk_prover* p, size_t B) {
     return p->seg_forced ? 1u << (p->seg_forced - 1) : prover_plan_segments(device_cus(p->ctx->device), p->log_n, B);
-}
-
-// the segmented grand product: seg = 2 B S + B elements of scratch (numerator carries, denominator carries, the inversions)
-static int launch_grand_product_segmented(hipStream_t s, const GrandProductIn& gp, const Fr* roots, const ProofState* st,
-                                          const RoundChallenges& direct, size_t n, size_t B, unsigned S, Fr* z_out, uint32_t* closes,
-                                          Fr* num, Fr* den, Fr* seg) {
-    Fr *seg_n = seg, *seg_d = seg + B * S, *tot_inv = seg + 2 * B * S;
-    PLONK_LAUNCH(gp_seg_factors_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, gp, roots, st, direct, n, num, den, seg_n, seg_d);
-    PLONK_LAUNCH(gp_seg_carries_kernel, dim3((unsigned)B), dim3(SEG_THREADS), 0, s, S, seg_n, seg_d, tot_inv, closes);
-    PLONK_LAUNCH(gp_seg_apply_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, n, (const Fr*)seg_n, (const Fr*)seg_d,
-                 (const Fr*)tot_inv, (const Fr*)num, den, z_out);
-    return PLONK_OK;
 }
 
 static void free_batch(plonk_prover* p) {
@@ -871,11 +388,9 @@ static void free_batch(plonk_prover* p) {
     p->cap_b = 0;
 }
 
-// the carries and partial sums of the segmented scans: 7 B S elements (the evaluations' seven partial sums per segment; the grand
-// product takes 2 B S + B of them, the two divisions 2 B S), none while S = 1
+// the carries and partial sums of the segmented scans (prover_scans.h: scan_scratch_elems)
 static int ensure_segments(plonk_prover* p, size_t B) {
-    const unsigned S = prover_segments(p, B);
-    const size_t need = S > 1 ? (size_t)NEVAL * B * S + B : 0;
+    const size_t need = scan_scratch_elems(B, prover_segments(p, B));
     if (need <= p->seg_cap) return PLONK_OK;
     PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
     dev_free_all({(void**)&p->seg});
@@ -1161,7 +676,7 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     uint8_t* cfl = p->commit_flags;
     PLONK_REQUIRE(B <= 65535, PLONK_ERR_ARG, "batch %zu exceeds 65535 (the proofs are a grid's second dimension)", B);
     PLONK_TRY(ensure_segments(p, B));  // (the options may have changed since the upload)
-    const unsigned S = prover_segments(p, B);  // 1: the one-workgroup scans
+    const unsigned S = prover_segments(p, B);  // of the three scans (prover_scans.h); 1: one workgroup per proof
 
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 0, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
@@ -1189,12 +704,8 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     }
     // (the three scan families are instrumented for plonk_profile_read: tools/prover_scale.py)
     PLONK_TRY(prof_begin(ctx, "prover_grand_product", 11.0 * 32.0 * (double)n * (double)B));
-    if (S > 1)
-        PLONK_TRY(launch_grand_product_segmented(s, gp, p->roots, (const ProofState*)p->state, RoundChallenges{}, n, B, S, p->z_lag, p->closes,
-                                                 p->num, p->wz, p->seg));
-    else
-        PLONK_LAUNCH(grand_product_kernel, dim3((unsigned)B), dim3(GP_THREADS), 0, s, gp, p->roots, (const ProofState*)p->state,
-                     RoundChallenges{}, n, p->z_lag, p->closes, p->num, p->wz);  // num / wz: scratch until round 5
+    PLONK_TRY(scan_grand_product(s, S, gp, p->roots, p->state, RoundChallenges{}, n, B, p->z_lag, p->closes, p->num, p->wz,
+                                 p->seg));  // num / wz: scratch until round 5
     PLONK_TRY(prof_end(ctx));
     PLONK_TRY(ntt_run(ctx, p->z_lag, p->coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
     if (p->lag_srs) PLONK_TRY(msm_run_device(ctx, p->lag_srs, p->z_lag, n, B, n, cxy + 2 * 3 * B, cfl + 3 * B));
@@ -1236,14 +747,7 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 3, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 4: evaluations                                                  prover.py:228-239
     PLONK_TRY(prof_begin(ctx, "prover_evaluations", 7.0 * 32.0 * (double)n * (double)B));
-    if (S > 1) {
-        PLONK_LAUNCH(eval_seg_kernel, dim3(S, (unsigned)B), dim3(SEG_THREADS), 0, s, (const Fr*)p->coef, (const Fr*)p->fixed_coef, p->w,
-                     (const ProofState*)p->state, n, B, p->seg);
-        PLONK_LAUNCH(eval_seg_finish_kernel, dim3((unsigned)B), dim3(SEG_THREADS), 0, s, (const Fr*)p->seg, S, p->state);
-    } else {
-        PLONK_LAUNCH(eval_kernel, dim3((unsigned)B), dim3(EV_THREADS), 0, s, (const Fr*)p->coef, (const Fr*)p->fixed_coef, p->w,
-                     p->state, n, B);
-    }
+    PLONK_TRY(scan_evaluations(s, S, p->coef, p->fixed_coef, p->w, p->state, n, B, p->seg));
     PLONK_TRY(prof_end(ctx));
     PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 4, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
     // ---- round 5: opening polynomials in coefficient form, commit              prover.py:241-306
@@ -1253,18 +757,8 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_LAUNCH(linearisation_kernel, dim3(gx, (unsigned)B), dim3(256), 0, s, (const Fr*)p->coef,
                  (const Fr*)p->fixed_coef, (const Fr*)p->quot, (const LinWeights*)lw, log_n, B, p->num);
     PLONK_TRY(prof_begin(ctx, "prover_divisions", 2.0 * 3.0 * 32.0 * (double)n * (double)B));
-    if (S > 1) {  // both openings share the launches (blockIdx.z)
-        const DivideIn dv = {{p->num, p->coef + 4 * B * n}, {p->wz, p->wz + B * n}};
-        PLONK_LAUNCH(divide_seg_horner_kernel, dim3(S, (unsigned)B, 2), dim3(SEG_THREADS), 0, s, dv, p->w, (const ProofState*)p->state, n, p->seg);
-        PLONK_LAUNCH(divide_seg_carries_kernel, dim3((unsigned)B, 1, 2), dim3(SEG_THREADS), 0, s, S, p->w, (const ProofState*)p->state, n, p->seg);
-        PLONK_LAUNCH(divide_seg_apply_kernel, dim3(S, (unsigned)B, 2), dim3(SEG_THREADS), 0, s, dv, p->w, (const ProofState*)p->state, n,
-                     (const Fr*)p->seg);
-    } else {
-        PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)p->num, n, 0, p->w,
-                     (const ProofState*)p->state, n, p->wz);
-        PLONK_LAUNCH(divide_linear_kernel, dim3((unsigned)B), dim3(DV_THREADS), 0, s, (const Fr*)(p->coef + 4 * B * n), n, 1,
-                     p->w, (const ProofState*)p->state, n, p->wz + B * n);
-    }
+    const DivideIn dv = {{p->num, p->coef + 4 * B * n}, {p->wz, p->wz + B * n}};  // W_z's numerator by X - zeta, Z by X - zeta w
+    PLONK_TRY(scan_divisions(s, S, dv, p->w, p->state, n, B, p->seg));
     PLONK_TRY(prof_end(ctx));
     PLONK_TRY(msm_run_device(ctx, p->srs, p->wz, n, 2 * B, n, cxy + 2 * 7 * B, cfl + 7 * B));
     PLONK_CHECK_HIP(hipGetLastError());
@@ -1335,7 +829,7 @@ int plonk_fr_grand_product(plonk_ctx* ctx, const void* d_a, const void* d_b, con
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &roots));
     void* scratch;
     const unsigned S = prover_plan_segments(device_cus(ctx->device), log_n, 1);
-    PLONK_TRY(ctx_scratch(ctx, 2, (2 * n + 2 + 2 * S + 1) * sizeof(Fr), &scratch));  // num, den, the closes flag, the segments' carries
+    PLONK_TRY(ctx_scratch(ctx, 2, (2 * n + 2 + scan_scratch_elems(1, S)) * sizeof(Fr), &scratch));  // num, den, the closes flag, the segments' carries
     Fr* num = (Fr*)scratch;
     uint32_t* closes = reinterpret_cast<uint32_t*>(num + 2 * n);
     GrandProductIn gp = {{(const Fr*)d_a, (const Fr*)d_b, (const Fr*)d_c}, {(const Fr*)d_s1, (const Fr*)d_s2, (const Fr*)d_s3}};
@@ -1343,11 +837,7 @@ int plonk_fr_grand_product(plonk_ctx* ctx, const void* d_a, const void* d_b, con
     ch.beta = fr_from_le32(beta_le32);
     ch.gamma = fr_from_le32(gamma_le32);
     ch.alpha = fp_zero<FrParams>();
-    if (S > 1)
-        PLONK_TRY(launch_grand_product_segmented(ctx->stream, gp, roots, nullptr, ch, n, 1, S, (Fr*)d_z_out, closes, num, num + n, num + 2 * n + 2));
-    else
-        PLONK_LAUNCH(grand_product_kernel, dim3(1), dim3(GP_THREADS), 0, ctx->stream, gp, roots, (const ProofState*)nullptr, ch, n,
-                     (Fr*)d_z_out, closes, num, num + n);
+    PLONK_TRY(scan_grand_product(ctx->stream, S, gp, roots, nullptr, ch, n, 1, (Fr*)d_z_out, closes, num, num + n, num + 2 * n + 2));
     PLONK_CHECK_HIP(hipGetLastError());
     uint32_t c = 0;
     PLONK_CHECK_HIP(hipMemcpyAsync(&c, closes, sizeof c, hipMemcpyDeviceToHost, ctx->stream));

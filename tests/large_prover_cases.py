@@ -1,4 +1,4 @@
-"""Bodies of the lock-step prover's tests above 2^12 and of the segmented per-proof scans (csrc/prover.hip): shared by
+"""Bodies of the lock-step prover's tests above 2^12 and of the segmented per-proof scans (csrc/prover_scans.h): shared by
 tests/test_gpu_prover_large.py (MI355X) and tests/test_emu_prover_segments.py (emulated kernels, fpl.h's range assertions)."""
 import ctypes
 import random
@@ -95,8 +95,10 @@ def corrupted_cell_status(setup, n, S, cells):
 
 def grand_product_vs_integers(log_n, seed=1600):
     """plonk_fr_grand_product against Z_{i+1} = Z_i num_i / den_i in Python integers (ratio 0 where den_i = 0), zero denominators
-    planted at row 0, row n - 1 and both sides of every boundary of the automatic segmentation; then once more without them, with
-    sigma = the identity permutation's columns, so that the product closes: out_closes both ways."""
+    planted at row 0, row n - 1 and both sides of every boundary of the automatic segmentation, or, where that is S = 1, of the
+    boundaries of the one workgroup's lane chunks (per = max(n / 256, 1) rows each) before lanes 1, 128 and 255, where those rows
+    exist; then once more without them, with sigma = the identity permutation's columns, so that the product closes: out_closes both
+    ways.  Returns S."""
     ctx = pa.get_context()
     n = 1 << log_n
     S = plan_segments(log_n, 1)
@@ -136,7 +138,11 @@ def grand_product_vs_integers(log_n, seed=1600):
     vec = lambda: [rng.randrange(R_MOD) for _ in range(n)]
     A, B, C, S1, S2, S3 = (vec() for _ in range(6))
     L = n // S
-    planted = sorted({0, n - 1} | {s * L - 1 for s in range(1, S)} | {s * L for s in range(1, S)})
+    planted = {0, n - 1} | {s * L - 1 for s in range(1, S)} | {s * L for s in range(1, S)}
+    if S == 1:
+        per = max(n // 256, 1)
+        planted |= {r for t in (1, 128, 255) for r in (per * t - 1, per * t) if r < n}
+    planted = sorted(planted)
     for i in planted:
         A[i] = (-(beta * S1[i] + gamma)) % R_MOD
     Z, closes_want, den = expect(A, B, C, S1, S2, S3)

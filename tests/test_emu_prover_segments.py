@@ -1,4 +1,4 @@
-"""The segmented per-proof scans of the lock-step prover (csrc/prover.hip) on the emulated kernels: the new lazy-limb code of the
+"""The segmented per-proof scans of the lock-step prover (csrc/prover_scans.h) on the emulated kernels: the new lazy-limb code of the
 segmented evaluation runs under fpl.h's range assertions here, and a forced S must give the bytes of S = 1."""
 import pytest
 
@@ -11,6 +11,13 @@ def test_forced_segments_equal_one_workgroup(emu, n, S):
     from plonkathon_amd import Setup
 
     lc.forced_segments_equal_one_workgroup(Setup.from_file(lc.PTAU), n, S, B=2)
+
+
+@pytest.mark.parametrize("log_n", [5, 8, 10])
+def test_grand_product_one_workgroup_vs_integers(emu, log_n):
+    """S = 1: fewer rows than lanes (idle lanes carry the neutral element), one row per lane, four rows per lane."""
+    assert lc.plan_segments(log_n, 1) == 1
+    assert lc.grand_product_vs_integers(log_n) == 1
 
 
 def test_segment_options_are_checked(emu):

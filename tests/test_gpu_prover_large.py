@@ -1,4 +1,4 @@
-"""The lock-step prover from 2^13 to 2^16 rows and the segmented forms of its three per-proof scans (csrc/prover.hip), on an
+"""The lock-step prover from 2^13 to 2^16 rows and the segmented forms of its three per-proof scans (csrc/prover_scans.h), on an
 MI355X.  Fixtures: tests/golden/oracle_proofs_large.json (tools/gen_oracle_proofs_large.py: the oracle's proofs at 2^13 and 2^14,
 91 s and 184 s on one core).  2^16 has no oracle proof: it is checked by the pairing verifiers and against the S = 1 run."""
 import time
@@ -81,6 +81,13 @@ def test_plan_leaves_the_benchmarked_shapes_alone():
 def test_grand_product_segmented_vs_integers(log_n):
     assert lc.plan_segments(log_n, 1) > 1  # these calls do take the segmented form
     assert lc.grand_product_vs_integers(log_n) > 1
+
+
+@pytest.mark.parametrize("log_n", [5, 8, 10])
+def test_grand_product_one_workgroup_vs_integers(log_n):
+    """S = 1: fewer rows than lanes (idle lanes carry the neutral element), one row per lane, four rows per lane."""
+    assert lc.plan_segments(log_n, 1) == 1
+    assert lc.grand_product_vs_integers(log_n) == 1
 
 
 # ---- 2^13 and 2^14 against the oracle's proofs -----------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The lock-step prover from 2^12 to 2^16 rows at small batches, and the evidence behind prover_plan_segments (csrc/prover.hip).
+"""The lock-step prover from 2^12 to 2^16 rows at small batches, and the evidence behind prover_plan_segments (csrc/prover_scans.h).
 
   --mode grid    n = 2^12 .. 2^16 x B in {1, 8, 64}: milliseconds per plonk_prover_run (median, min, max of 5 after a warm-up, HIP
                  events on the prover's stream), proofs/s, and the three per-proof scan families' own times (plonk_profile_*:
