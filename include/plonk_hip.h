@@ -269,6 +269,31 @@ int plonk_prover_upload_variables(plonk_prover* p, const uint8_t* vars_le32, siz
  * (plonk_host_alloc) — a pageable buffer makes the copy synchronous again.  A value that is not below r cannot be
  * reported here: it sets status bit 3 of the proof it belongs to at plonk_prover_download.                       */
 int plonk_prover_upload_variables_async(plonk_prover* p, const uint8_t* vars_le32, size_t batch);
+/* The witness solver: a batch from the circuit's INPUT values alone, 32 * n_inputs bytes per proof.  The device fills in every
+ * other variable as Program.fill_variable_assignments does (compiler/program.py:161-192): row by row in program order, wherever
+ * QO = +-1, the gate identity is solved for the output wire, c = -(QL a + QR b + QM a b + QC) / QO; a row whose output is
+ * already known is a check instead.
+ *   plonk_prover_set_inputs   after plonk_prover_set_wiring: input_index[n_inputs] = the variables a batch gives values for.
+ *                         Builds the plan from the gate columns plonk_prover_create was given.  PLONK_ERR_ARG with
+ *                         *out_missing_var = a variable when a row reads it before an input or an earlier row has given it a
+ *                         value (the reference's KeyError) or when no row ever does; PLONK_ERR_ARG with *out_missing_var =
+ *                         0xffffffff for an index out of range or given twice.
+ *   plonk_prover_upload_inputs   inputs_le32 = [batch][n_inputs] canonical LE, in the order of input_index.  Seeds the inputs,
+ *                         solves, then gathers wire columns and public inputs as plonk_prover_upload_variables does; waits.  A
+ *                         value that is not below r: PLONK_ERR_ARG, no batch resident.  PLONK_ERR_STATE before set_wiring /
+ *                         set_inputs.  A failed check does not fail the call: it is status bit 4 of plonk_prover_download.
+ *   plonk_prover_upload_inputs_async   the contract of plonk_prover_upload_variables_async: copy stream, no host wait, page-locked
+ *                         memory that stays valid until the batch is downloaded; a value that is not below r is status bit 3.
+ *   plonk_prover_download_variables   [batch][k] canonical LE values of the variables var_index[0 .. k) of the resident batch
+ *                         (var_index == NULL: all n_vars in order, k ignored), after plonk_prover_upload_inputs* or
+ *                         plonk_prover_upload_variables*: e.g. a public input the solver computed, which the verifier needs.
+ *   plonk_prover_solve_failures   out_rows[batch]: 0, or 1 + the first row whose check failed (status bit 4 = the witness solver's
+ *                         check failed: the reference raises "Failed assertion" there; never set after the other uploads).   */
+int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t n_inputs, uint32_t* out_missing_var);
+int plonk_prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t batch);
+int plonk_prover_upload_inputs_async(plonk_prover* p, const uint8_t* inputs_le32, size_t batch);
+int plonk_prover_download_variables(plonk_prover* p, size_t batch, const uint32_t* var_index, size_t k, uint8_t* out_le32);
+int plonk_prover_solve_failures(plonk_prover* p, size_t batch, uint32_t* out_rows);
 int plonk_prover_run(plonk_prover* p, size_t batch);
 int plonk_prover_download(plonk_prover* p, size_t batch, uint8_t* out_proofs, uint8_t* out_status);
 int plonk_prover_challenges(plonk_prover* p, size_t b, uint8_t out_le32[6 * 32]);

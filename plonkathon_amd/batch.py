@@ -78,6 +78,8 @@ class BatchProver:
                                                      len(self._vars)))
             self._getter = True
             self._var_keys = tuple(self._vars)
+        self._pos = pos
+        self._input_keys = None  # set_inputs / the first upload_inputs
 
     def __del__(self):
         try:
@@ -137,6 +139,83 @@ class BatchProver:
         check(self.ctx.L.plonk_prover_upload_variables_async(self._h, ctypes.addressof(pinned), B))
         self._resident = B
 
+    # ---- inputs only: the device solves for every other variable (csrc/witness_solve.h) -----------------
+    def set_inputs(self, names):
+        """The circuit's inputs: the variables `upload_inputs` / `upload_input_values` give values for, in that order.
+        Names that are not variables of the circuit are dropped (the reference's filler carries them along unused).  The
+        device then computes every other variable as `Program.fill_variable_assignments` does.  KeyError(name): a row reads
+        that variable before anything gives it a value, or nothing ever does — the filler's KeyError."""
+        keys = tuple(k for k in names if k in self._pos)
+        idx = np.ascontiguousarray([self._pos[k] for k in keys], dtype=np.uint32)
+        missing = ctypes.c_uint32(0xFFFFFFFF)
+        rc = self.ctx.L.plonk_prover_set_inputs(self._h, idx.ctypes.data if len(idx) else None, len(idx), ctypes.byref(missing))
+        if rc == _lib.PLONK_ERR_ARG and missing.value != 0xFFFFFFFF:
+            raise KeyError(self._vars[missing.value])
+        check(rc)
+        self._input_keys = keys
+        self._resident = 0
+
+    @property
+    def inputs(self):
+        """The input names in the column order `upload_input_values` expects (None before `set_inputs`)."""
+        return self._input_keys
+
+    def upload_inputs(self, assignments):
+        """Stage a batch from the circuit's inputs alone: one dict of input values per proof (32 bytes per input and proof
+        go to the device).  The first call sets the inputs from the first dict's keys that are variables of the circuit;
+        a later dict that lacks one of them is a KeyError."""
+        if self._input_keys is None:
+            self.set_inputs(list(assignments[0]))
+        B = len(assignments)
+        enc = _pack_witnesses(assignments, self._input_keys, R_MOD)
+        check(self.ctx.L.plonk_prover_upload_inputs(self._h, enc, B))
+        self._resident = B
+
+    def upload_input_values(self, blob, B):
+        """The same staging from packed bytes: `blob` = [B][K] canonical 32-byte little-endian values in the order of
+        `self.inputs`."""
+        K = len(self._input_keys or ())
+        if self._input_keys is not None and len(blob) != 32 * B * K:
+            raise ValueError("upload_input_values: expected %d bytes" % (32 * B * K))
+        check(self.ctx.L.plonk_prover_upload_inputs(self._h, blob, B))
+        self._resident = B
+
+    def upload_input_values_async(self, pinned, B):
+        """upload_input_values without a host wait, as `upload_values_async`: `pinned` = a Context.host_alloc buffer that
+        stays untouched until this batch has been downloaded; a non-canonical value shows up as status bit 3."""
+        K = len(self._input_keys or ())
+        if self._input_keys is not None and len(pinned) < 32 * B * K:
+            raise ValueError("upload_input_values_async: expected %d bytes" % (32 * B * K))
+        check(self.ctx.L.plonk_prover_upload_inputs_async(self._h, ctypes.addressof(pinned), B))
+        self._resident = B
+
+    def variable_values(self, names=None, B=None):
+        """The resident batch's variable values, one dict name -> int per proof (all variables, or `names`): what the
+        solver computed, after `upload_inputs*`; what was uploaded, after `upload` / `upload_values*`."""
+        B = self._resident if B is None else B
+        names = self._vars if names is None else list(names)
+        idx = None if names is self._vars else np.ascontiguousarray([self._pos[k] for k in names], dtype=np.uint32)
+        k = len(names)
+        out = ctypes.create_string_buffer(32 * B * max(k, 1))
+        check(self.ctx.L.plonk_prover_download_variables(self._h, B, None if idx is None else idx.ctypes.data, k, out))
+        raw = out.raw
+        return [{name: int.from_bytes(raw[32 * (b * k + j) : 32 * (b * k + j + 1)], "little") for j, name in enumerate(names)}
+                for b in range(B)]
+
+    def public_values(self, B=None):
+        """The resident batch's public inputs in the order of the public rows, one list of ints per proof: what
+        `VerificationKey.verify_proof` takes — a public variable the solver computed (a hash, say) among them."""
+        if not self._public_vars:
+            return [[] for _ in range(self._resident if B is None else B)]
+        return [[w[v] for v in self._public_vars] for w in self.variable_values(self._public_vars, B)]
+
+    def solve_failures(self, B=None):
+        """Per proof of the resident batch: None, or the row whose check failed first in the solver (status bit 16)."""
+        B = self._resident if B is None else B
+        rows = (ctypes.c_uint32 * B)()
+        check(self.ctx.L.plonk_prover_solve_failures(self._h, B, rows))
+        return [r - 1 if r else None for r in rows]
+
     @property
     def variables(self):
         """Variable names in the column order `upload_values` expects."""
@@ -190,6 +269,10 @@ class BatchProver:
         for b, st in enumerate(status):
             if st & 8:
                 raise ProofError("proof %d: an uploaded witness value is not a canonical Fr value (>= r)" % b)
+            if st & 16:
+                row = self.solve_failures(len(status))[b]
+                raise ProofError("proof %d: failed assertion at row %d (%s): the value given for its output is not the one "
+                                 "the row computes (compiler/program.py:185-186)" % (b, row, getattr(self.program, "source", {row: "?"})[row]))
             if st & 4:
                 raise ProofError("proof %d: witness does not satisfy the gate constraints "
                                  "(prover.py:108-116, checked row by row; it is what the quotient-degree assert of prover.py:205-208 detects)" % b)
@@ -221,6 +304,12 @@ class BatchProver:
 
     def prove_batch(self, witnesses):
         self.upload(witnesses)
+        self.run()
+        return self.download()
+
+    def prove_inputs(self, assignments):
+        """prove_batch from the circuit's inputs alone (`upload_inputs`)."""
+        self.upload_inputs(assignments)
         self.run()
         return self.download()
 

@@ -219,6 +219,7 @@ class Program:
         if len(constraints) > group_order:
             raise Exception("Group order too small")
         self.constraints = [eq_to_assembly(c) for c in constraints]
+        self.source = [str(c).rstrip("\n") for c in constraints]  # row -> its constraint text, for error messages
         self.group_order = group_order
 
     @classmethod

@@ -23,6 +23,7 @@ struct RoundChallenges { Fr beta, gamma, alpha; };
 #define PROVER_ST_Z_OPEN 2u     // Z does not close to 1: the witness breaks the copy constraints (prover.py:132)
 #define PROVER_ST_GATE 4u       // a gate constraint fails on some row (prover.py:108-116)
 #define PROVER_ST_BAD_INPUT 8u  // an asynchronously uploaded value was not below r
+#define PROVER_ST_ASSERT 16u    // the witness solver's check of a row whose output was already known failed (compiler/program.py:185-186)
 
 // A proof record: nine commitments a_1, b_1, c_1, z_1, t_lo_1, t_mid_1, t_hi_1, W_z_1, W_zw_1, then the six evaluations a, b, c,
 // s1, s2, z_shifted.  Plain: x || y and the evaluations as canonical little-endian words.  Compressed (g1_codec.h): 32 bytes per
@@ -92,6 +93,21 @@ struct plonk_prover {
     unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
     hipEvent_t ev_copied, ev_vars_read;  // async upload: the copy stream's H2D is done / the gather kernels have read `vars`
     bool vars_read_pending;
+    size_t bad_stride;         // values per proof of the last upload that ran the checked conversion: *bad_input / bad_stride owns the bad value
+    bool vars_valid;           // `vars` holds the resident batch (not after plonk_prover_upload_witness)
+    // the witness solver (witness_solve.h; plonk_prover_set_inputs, plonk_prover_upload_inputs)
+    uint8_t* gates_host;       // [5][n] canonical LE: QM, QL, QR, QO, QC as plonk_prover_create was given them
+    uint32_t* cell_host;       // [3][n] host copy of cell_index
+    uint32_t* solve_desc;      // [solve_rows] one descriptor per row (device)
+    uint32_t solve_rows;       // rows the solver walks: up to the last one that is not skipped
+    uint32_t* input_index;     // [n_inputs] the input variables (device)
+    size_t n_inputs;           // 0: no plan (plonk_prover_set_inputs has not been called since the wiring was set)
+    Fr* inputs;                // [B][n_inputs] staging of the uploaded input values (canonical, as copied)
+    uint32_t* solve_bad;       // [B] 0, or 1 + the first row whose check failed
+    size_t inputs_cap;         // proofs `inputs` and `solve_bad` hold
+    bool solve_valid;          // the resident batch came through the solver: solve_bad belongs to it
+    hipEvent_t ev_inputs_read; // async upload: the seed kernel has read `inputs`
+    bool inputs_read_pending;
     Fq *commit_xy; // [9][B] x||y canonical
     uint8_t* commit_flags;  // [9][B]
     ProofState* state;      // [B]

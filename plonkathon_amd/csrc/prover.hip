@@ -21,6 +21,7 @@
 #include "prover.h"
 #include "g1_codec.h"
 #include "prover_scans.h"  // rounds 2, 4 and 5: the grand product, the evaluations, the divisions — kernels and launchers
+#include "witness_solve.h"  // the variables of a batch from its input values: the plan, the solver's kernels
 
 // ------------------------------------------------------------------------------------------------
 // witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
@@ -355,9 +356,10 @@ __global__ void pack_proofs_kernel(const Fq* commit_xy, const ProofState* st, si
     }
 }
 
-// the status byte of every proof (PROVER_ST_*); closes = plonk_prover::closes
+// the status byte of every proof (PROVER_ST_*); closes = plonk_prover::closes; bad_stride = values per proof of the upload that
+// filled *bad_input; solve_bad = plonk_prover::solve_bad, or null for a batch that did not come through the solver
 __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes, const uint8_t* flags, const unsigned long long* bad_input,
-                                   size_t n_vars, size_t B, uint8_t* out) {
+                                   size_t bad_stride, const uint32_t* solve_bad, size_t B, uint8_t* out) {
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     uint8_t f = 0;
@@ -365,7 +367,8 @@ __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes,
     if (st[b].error) f |= PROVER_ST_IDENTITY;
     if (!closes[b]) f |= PROVER_ST_Z_OPEN;
     if (closes[B + b]) f |= PROVER_ST_GATE;
-    if (bad_input && *bad_input != ~0ull && n_vars && *bad_input / n_vars == b) f |= PROVER_ST_BAD_INPUT;
+    if (bad_input && *bad_input != ~0ull && bad_stride && *bad_input / bad_stride == b) f |= PROVER_ST_BAD_INPUT;
+    if (solve_bad && solve_bad[b]) f |= PROVER_ST_ASSERT;
     out[b] = f;
 }
 
@@ -482,6 +485,9 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
     PLONK_TRY(dev_alloc((void**)&p->g_pow, n3 * e));
     PLONK_TRY(dev_alloc((void**)&p->ginv_pow, n3 * e));
     PLONK_TRY(plonk_fr_upload(ctx, p->fixed_lag, selectors_le32, 8 * n));
+    p->gates_host = (uint8_t*)malloc(5 * n * 32);  // QM .. QC as given: what plonk_prover_set_inputs classifies
+    PLONK_REQUIRE(p->gates_host, PLONK_ERR_NOMEM, "out of host memory");
+    memcpy(p->gates_host, selectors_le32, 5 * n * 32);
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &p->roots));
     const Fr one = fp_one<FrParams>();
     const Fr mu = host_root_of_unity(log_n + 2, false);
@@ -551,7 +557,11 @@ int plonk_prover_destroy(plonk_prover* p) {
     }
     free_batch(p);
     dev_free_all({(void**)&p->fixed_lag, (void**)&p->fixed_coef, (void**)&p->fixed_big, (void**)&p->l0_big, (void**)&p->x_big, (void**)&p->g_pow,
-                  (void**)&p->ginv_pow, (void**)&p->li_big, (void**)&p->cell_index, (void**)&p->pub_index});
+                  (void**)&p->ginv_pow, (void**)&p->li_big, (void**)&p->cell_index, (void**)&p->pub_index, (void**)&p->solve_desc,
+                  (void**)&p->input_index, (void**)&p->inputs, (void**)&p->solve_bad});
+    free(p->gates_host);
+    free(p->cell_host);
+    if (p->ev_inputs_read) hipEventDestroy(p->ev_inputs_read);
     if (p->bad_input) {
         hipFree(p->bad_input);
         hipEventDestroy(p->ev_copied);
@@ -585,6 +595,7 @@ int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const 
     PLONK_TRY(fill_pi_column(p, B));
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     p->resident_b = B;
+    p->vars_valid = p->solve_valid = false;
     return PLONK_OK;
 }
 
@@ -603,7 +614,12 @@ int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const u
     if (p->n_public)
         PLONK_CHECK_HIP(hipMemcpyAsync(p->pub_index, public_index, p->n_public * sizeof(uint32_t), hipMemcpyHostToDevice, p->ctx->stream));
     PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
+    if (!p->cell_host) p->cell_host = (uint32_t*)malloc(3 * p->n * sizeof(uint32_t));
+    PLONK_REQUIRE(p->cell_host, PLONK_ERR_NOMEM, "out of host memory");
+    memcpy(p->cell_host, cell_index, 3 * p->n * sizeof(uint32_t));
     p->n_vars = n_vars;
+    p->n_inputs = 0;  // a plan belongs to the wiring it was built from
+    p->vars_valid = false;
     return PLONK_OK;
 }
 
@@ -614,13 +630,11 @@ int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const u
 // follow on the compute stream behind an event, nothing waits on the host; the canonical-range verdict stays on the
 // device and comes back as PROVER_ST_BAD_INPUT of plonk_prover_download.  The caller keeps vars_le32 alive (and, for a copy
 // that really is asynchronous, in pinned memory: plonk_host_alloc) until the batch has been downloaded.
-static int prover_upload_vars(plonk_prover* p, const uint8_t* vars_le32, size_t B, bool async) {
-    PLONK_REQUIRE(p && vars_le32 && B, PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
-    PLONK_REQUIRE(p->n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+// the per-batch buffers, `vars` [B][n_vars] and what the checked conversion and the asynchronous uploads need
+static int ensure_vars(plonk_prover* p, size_t B) {
     PLONK_TRY(ensure_batch(p, B));
     plonk_ctx* ctx = p->ctx;
-    const size_t n = p->n, V = p->n_vars;
+    const size_t V = p->n_vars;
     if (p->vars_cap < B * V) {
         PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         dev_free_all({(void**)&p->vars});
@@ -633,7 +647,34 @@ static int prover_upload_vars(plonk_prover* p, const uint8_t* vars_le32, size_t 
         PLONK_CHECK_HIP(hipEventCreate(&p->ev_copied));
         PLONK_CHECK_HIP(hipEventCreate(&p->ev_vars_read));
     }
+    return PLONK_OK;
+}
+
+// the wire columns, the public inputs and the PI column from `vars`; ev_vars_read marks the last read of `vars`
+static int gather_from_vars(plonk_prover* p, size_t B) {
+    plonk_ctx* ctx = p->ctx;
+    const size_t n = p->n, V = p->n_vars;
+    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, ctx->stream, (const Fr*)p->vars, (const uint32_t*)p->cell_index, V,
+                 n, B, p->wit_lag);
+    if (p->n_public)
+        PLONK_LAUNCH(public_gather_kernel, grid1(B * p->n_public), dim3(256), 0, ctx->stream, (const Fr*)p->vars,
+                     (const uint32_t*)p->pub_index, V, p->n_public, B, p->pub);
+    PLONK_TRY(fill_pi_column(p, B));
+    PLONK_CHECK_HIP(hipEventRecord(p->ev_vars_read, ctx->stream));
+    p->vars_read_pending = true;
+    return PLONK_OK;
+}
+
+static int prover_upload_vars(plonk_prover* p, const uint8_t* vars_le32, size_t B, bool async) {
+    PLONK_REQUIRE(p && vars_le32 && B, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(p->ctx);
+    PLONK_REQUIRE(p->n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    PLONK_TRY(ensure_vars(p, B));
+    plonk_ctx* ctx = p->ctx;
+    const size_t V = p->n_vars;
     p->resident_b = 0;  // until the new batch is in place (a failed upload leaves no batch to run)
+    p->vars_valid = p->solve_valid = false;
+    p->bad_stride = V;
     if (async) {
         PLONK_TRY(ctx_copy_stream(ctx));
         if (p->vars_read_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->copy_stream, p->ev_vars_read, 0));  // the previous gather has read vars
@@ -645,21 +686,143 @@ static int prover_upload_vars(plonk_prover* p, const uint8_t* vars_le32, size_t 
         PLONK_CHECK_HIP(hipMemsetAsync(p->bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
         PLONK_TRY(plonk_fr_upload(ctx, p->vars, vars_le32, B * V));  // waits, and reports a non-canonical value as PLONK_ERR_ARG
     }
-    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, ctx->stream, (const Fr*)p->vars, (const uint32_t*)p->cell_index, V,
-                 n, B, p->wit_lag);
-    if (p->n_public)
-        PLONK_LAUNCH(public_gather_kernel, grid1(B * p->n_public), dim3(256), 0, ctx->stream, (const Fr*)p->vars,
-                     (const uint32_t*)p->pub_index, V, p->n_public, B, p->pub);
-    PLONK_TRY(fill_pi_column(p, B));
-    PLONK_CHECK_HIP(hipEventRecord(p->ev_vars_read, ctx->stream));
-    p->vars_read_pending = true;
+    PLONK_TRY(gather_from_vars(p, B));
     if (!async) PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     p->resident_b = B;
+    p->vars_valid = true;
     return PLONK_OK;
 }
 
 int plonk_prover_upload_variables(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload_vars(p, vars_le32, B, false); }
 int plonk_prover_upload_variables_async(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload_vars(p, vars_le32, B, true); }
+
+// ---- the witness solver (witness_solve.h) ----------------------------------------------------------------------------------
+// The circuit's inputs: the variables a batch will give values for.  Builds the solver's plan from the gate columns
+// plonk_prover_create was given and the wiring; a refusal that names a variable (one that no row assigns before it is read, or
+// at all) sets *out_missing_var to it, any other sets it to 0xffffffff.
+int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t n_inputs, uint32_t* out_missing_var) {
+    PLONK_REQUIRE(p && input_index && n_inputs && out_missing_var, PLONK_ERR_ARG, "bad argument");
+    *out_missing_var = SOLVE_NO_VARIABLE;
+    PLONK_ENTER(p->ctx);
+    PLONK_REQUIRE(p->n_vars && p->cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    plonk_ctx* ctx = p->ctx;
+    std::vector<uint32_t> desc;
+    PLONK_TRY(solve_plan_build(p->gates_host, p->cell_host, p->n, p->n_vars, input_index, n_inputs, desc, out_missing_var));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // a batch in flight still walks the old plan
+    p->n_inputs = 0;
+    p->resident_b = 0;
+    dev_free_all({(void**)&p->solve_desc, (void**)&p->input_index, (void**)&p->inputs, (void**)&p->solve_bad});
+    p->inputs_cap = 0;
+    PLONK_TRY(dev_alloc((void**)&p->solve_desc, desc.size() * sizeof(uint32_t)));
+    PLONK_TRY(dev_alloc((void**)&p->input_index, n_inputs * sizeof(uint32_t)));
+    if (!desc.empty())
+        PLONK_CHECK_HIP(hipMemcpyAsync(p->solve_desc, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipMemcpyAsync(p->input_index, input_index, n_inputs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    p->solve_rows = (uint32_t)desc.size();
+    p->n_inputs = n_inputs;
+    return PLONK_OK;
+}
+
+// values of the n_inputs input variables of each witness, [B][n_inputs] canonical LE: seed -> solve -> the gathers of
+// plonk_prover_upload_variables.  async: the contract of plonk_prover_upload_variables_async — the copy on the copy stream behind
+// the previous batch's last read of the staging buffer, everything else behind an event on the compute stream, no host wait, a
+// value that is not below r reported as PROVER_ST_BAD_INPUT.
+static int prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B, bool async) {
+    PLONK_REQUIRE(p && inputs_le32 && B, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(p->ctx);
+    PLONK_REQUIRE(p->n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    PLONK_REQUIRE(p->n_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
+    PLONK_TRY(ensure_vars(p, B));
+    plonk_ctx* ctx = p->ctx;
+    const size_t V = p->n_vars, K = p->n_inputs;
+    if (p->inputs_cap < B) {
+        PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        dev_free_all({(void**)&p->inputs, (void**)&p->solve_bad});
+        p->inputs_cap = 0;
+        PLONK_TRY(dev_alloc((void**)&p->inputs, B * K * sizeof(Fr)));
+        PLONK_TRY(dev_alloc((void**)&p->solve_bad, B * sizeof(uint32_t)));
+        p->inputs_cap = B;
+    }
+    if (!p->ev_inputs_read) PLONK_CHECK_HIP(hipEventCreate(&p->ev_inputs_read));
+    p->resident_b = 0;  // until the new batch is in place
+    p->vars_valid = p->solve_valid = false;
+    p->bad_stride = K;
+    hipStream_t s = ctx->stream;
+    if (async) {
+        PLONK_TRY(ctx_copy_stream(ctx));
+        if (p->inputs_read_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->copy_stream, p->ev_inputs_read, 0));  // the previous seed has read inputs
+        PLONK_CHECK_HIP(hipMemcpyAsync(p->inputs, inputs_le32, B * K * sizeof(Fr), hipMemcpyHostToDevice, ctx->copy_stream));
+        PLONK_CHECK_HIP(hipEventRecord(p->ev_copied, ctx->copy_stream));
+        PLONK_CHECK_HIP(hipStreamWaitEvent(s, p->ev_copied, 0));
+    } else {
+        PLONK_CHECK_HIP(hipMemcpyAsync(p->inputs, inputs_le32, B * K * sizeof(Fr), hipMemcpyHostToDevice, s));
+    }
+    PLONK_CHECK_HIP(hipMemsetAsync(p->bad_input, 0xff, sizeof(unsigned long long), s));
+    // (the solver writes `vars` in place: on the compute stream it is behind the previous batch's gathers, the only readers)
+    PLONK_LAUNCH(witness_seed_kernel, grid1(B * K), dim3(256), 0, s, (const Fr*)p->inputs, (const uint32_t*)p->input_index, K, V, B, p->vars,
+                 p->bad_input, p->solve_bad);
+    PLONK_CHECK_HIP(hipEventRecord(p->ev_inputs_read, s));
+    p->inputs_read_pending = true;
+    PLONK_TRY(prof_begin(ctx, "witness_solve", 32.0 * (double)V * (double)B));
+    PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, p->vars, (const uint32_t*)p->solve_desc,
+                 (const uint32_t*)p->cell_index, (const Fr*)p->fixed_lag, V, p->n, p->solve_rows, B, p->solve_bad);
+    PLONK_TRY(prof_end(ctx));
+    PLONK_TRY(gather_from_vars(p, B));
+    if (!async) {
+        unsigned long long first_bad = 0;
+        PLONK_CHECK_HIP(hipMemcpyAsync(&first_bad, p->bad_input, sizeof first_bad, hipMemcpyDeviceToHost, s));
+        PLONK_CHECK_HIP(hipStreamSynchronize(s));
+        PLONK_REQUIRE(first_bad == ~0ull, PLONK_ERR_ARG, "input %llu of proof %llu is not a canonical Fr value (>= r)", first_bad % K, first_bad / K);
+    }
+    p->resident_b = B;
+    p->vars_valid = p->solve_valid = true;
+    return PLONK_OK;
+}
+int plonk_prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload_inputs(p, inputs_le32, B, false); }
+int plonk_prover_upload_inputs_async(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload_inputs(p, inputs_le32, B, true); }
+
+// [B][k] canonical LE values of the variables var_index[0 .. k) of the resident batch (var_index == NULL: all n_vars, k
+// ignored), after either kind of variable upload: what the solver computed — a public input among it — for the verifier
+int plonk_prover_download_variables(plonk_prover* p, size_t B, const uint32_t* var_index, size_t k, uint8_t* out_le32) {
+    PLONK_REQUIRE(p && B && out_le32 && (k || !var_index), PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "download_variables: batch %zu, but %zu witnesses are resident", B, p->resident_b);
+    PLONK_REQUIRE(p->vars_valid, PLONK_ERR_STATE, "the resident batch was uploaded as wire columns: it has no variable values");
+    PLONK_ENTER(p->ctx);
+    plonk_ctx* ctx = p->ctx;
+    const size_t V = p->n_vars;
+    if (!var_index) k = V;
+    for (size_t j = 0; var_index && j < k; j++)
+        PLONK_REQUIRE(var_index[j] < V, PLONK_ERR_ARG, "index %zu names variable %u of %zu", j, var_index[j], V);
+    void* tmp;
+    PLONK_TRY(ctx_scratch(ctx, 3, B * k * sizeof(Fr) + k * sizeof(uint32_t), &tmp));
+    Fr* vals = (Fr*)tmp;
+    uint32_t* d_index = nullptr;
+    if (var_index) {
+        d_index = reinterpret_cast<uint32_t*>(vals + B * k);
+        PLONK_CHECK_HIP(hipMemcpyAsync(d_index, var_index, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    PLONK_LAUNCH(variable_gather_kernel, grid1(B * k), dim3(256), 0, ctx->stream, (const Fr*)p->vars, (const uint32_t*)d_index, V, k, B, vals);
+    PLONK_CHECK_HIP(hipGetLastError());
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_le32, vals, B * k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return PLONK_OK;
+}
+
+// per proof of the resident batch, 0 or 1 + the first row whose check failed (PROVER_ST_ASSERT); a batch that did not come
+// through the solver has none
+int plonk_prover_solve_failures(plonk_prover* p, size_t B, uint32_t* out_rows) {
+    PLONK_REQUIRE(p && B && out_rows, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "solve_failures: batch %zu, but %zu witnesses are resident", B, p->resident_b);
+    PLONK_ENTER(p->ctx);
+    if (!p->solve_valid) {
+        memset(out_rows, 0, B * sizeof(uint32_t));
+        return PLONK_OK;
+    }
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_rows, p->solve_bad, B * sizeof(uint32_t), hipMemcpyDeviceToHost, p->ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
+    return PLONK_OK;
+}
 
 // Enqueue all five rounds for the B resident witnesses.  Asynchronous.
 int plonk_prover_run(plonk_prover* p, size_t B) {
@@ -903,7 +1066,8 @@ int prover_pack_device(plonk_prover* p, size_t B, int compressed, uint8_t* d_pro
     PLONK_LAUNCH(pack_proofs_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const Fq*)p->commit_xy, (const ProofState*)p->state, B, d_proofs,
                  compressed ? 1 : 0);
     PLONK_LAUNCH(pack_status_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const ProofState*)p->state, (const uint32_t*)p->closes,
-                 (const uint8_t*)p->commit_flags, (const unsigned long long*)p->bad_input, p->n_vars, B, d_status);
+                 (const uint8_t*)p->commit_flags, (const unsigned long long*)p->bad_input, p->bad_stride,
+                 p->solve_valid ? (const uint32_t*)p->solve_bad : (const uint32_t*)nullptr, B, d_status);
     PLONK_CHECK_HIP(hipGetLastError());
     if (done) PLONK_CHECK_HIP(hipEventRecord(done, ctx->stream));
     return PLONK_OK;
