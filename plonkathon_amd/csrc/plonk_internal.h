@@ -52,6 +52,19 @@ static inline void dev_free_all(std::initializer_list<void**> ptrs) {
         *q = nullptr;
     }
 }
+// Grow device buffers that share one capacity (in the caller's units): nothing while `need` fits; otherwise wait for the stream
+// that may still be using them, free them, allocate each anew.  *cap is 0 while any of them is missing.
+struct DevBuf { void** ptr; size_t bytes; };
+static inline int dev_grow(hipStream_t stream, size_t* cap, size_t need, std::initializer_list<DevBuf> bufs) {
+    if (need <= *cap) return PLONK_OK;
+    PLONK_CHECK_HIP(hipStreamSynchronize(stream));
+    for (const DevBuf& b : bufs) dev_free_all({b.ptr});
+    *cap = 0;
+    for (const DevBuf& b : bufs)
+        if (int rc = dev_alloc(b.ptr, b.bytes)) return rc;
+    *cap = need;
+    return PLONK_OK;
+}
 
 static inline Fr host_fr_u64(uint64_t x) {  // a small integer in Montgomery form
     Fr a = fp_zero<FrParams>();

@@ -1,6 +1,8 @@
 // prover.h — what prover.hip and verifier.hip share (internal): the per-proof state, the resident batch, the status bits and the
 // layout of a proof record.
 #pragma once
+#include <type_traits>
+
 #include "plonk_internal.h"
 #include "transcript_device.h"
 
@@ -42,74 +44,93 @@ enum { FX_QM = 0, FX_QL, FX_QR, FX_QO, FX_QC, FX_S1, FX_S2, FX_S3, FX_COUNT };
 #define PROVER_MAX_LOG_N 16  // the largest group order the lock-step prover accepts: what the suite checks (tests/test_gpu_prover_large.py)
 #define QCOSETS 3  // cosets of size n the lock-step prover evaluates the quotient on (deg t < 3n)
 
-struct plonk_prover {
-    plonk_ctx* ctx;
-    plonk_srs* srs;
-    unsigned log_n;
-    size_t n, n_public;
-    Fr g;                // fixed coset offset (Montgomery)
-    Fr w, n_inv, half;   // the n-th root of unity, 1 / n, 1 / 2
-    // The quotient has degree < 3n, so THREE cosets of the n-th roots of unity determine it: x = g mu^r w^j, r < 3 (mu = the
-    // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.
-    Fr* fixed_lag;       // [8][n]   Lagrange values
-    Fr* fixed_coef;      // [8][n]   coefficient forms
-    Fr* fixed_big;       // [8][3][n]  the circuit polynomials on the three cosets
-    Fr* l0_big;          // [3][n]
-    Fr* x_big;           // [3][n]   the points g mu^r w^j
-    Fr* g_pow;           // [3][n]   (g mu^r)^i: the load-side scaling of the size-n transform that evaluates on coset r
-    Fr* ginv_pow;        // [3][n]   (g mu^r)^-i / 2n: the store-side scaling of the inverse transform of coset r (its 1/n folded in)
-    const Fr* roots;     // [n]      w^i (owned by ctx)
-    Fr zh_inv[QCOSETS];  // 1 / (g^n * i^r - 1): Z_H is constant on a coset
-    Fr comb_i, comb_g1, comb_g2;  // quotient_combine_kernel's constants: i = mu^n, 1 / g^n, 1 / g^2n
-    // Public inputs are the only non-zero entries of the PI column (prover.py:57-62): with few of them PI's
-    // coefficient and coset forms are cheaper from the Lagrange basis directly than through two transforms.
-    bool sparse_pi;      // n_public <= PI_SPARSE_MAX
-    Fr* li_big;          // [n_public][4n]  L_i on the coset: (w^i / n) Z_H(x_k) / (x_k - w^i)
-    const Fr* roots_inv; // [n]             w^-i (owned by ctx)
-    Fr* pub;             // [B][n_public]   public inputs of the resident batch (Montgomery)
-    // per-batch buffers (capacity cap_b proofs)
-    size_t cap_b;
-    Fr *wit_lag;   // [4][B][n]  A, B, C, PI   Lagrange
-    Fr *z_lag;     // [B][n]
-    Fr *coef;      // [5][B][n]  Ac, Bc, Cc, PIc, Zc   (coefficient forms; Z last so rounds 1 and 2 fill it in order)
-    Fr *big;       // [5][B][3][n] A, B, C, PI, Z on the three cosets
-    Fr *quot;      // [B][4n]    quotient evaluations on the three cosets, then its 3n coefficients (in place; the last n unused)
-    Fr *num;       // [B][n]     round 2: the grand product's numerator factors (the denominators' go to wz); round 5: W_z's numerator
-    uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
-    Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
-    struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
-    // the segmented scans (prover_scans.h): carries and partial sums of the S segments of every proof, none while S = 1
-    Fr* seg;                   // [scan_scratch_elems(B, S)]
-    size_t seg_cap;            // elements
-    unsigned seg_forced;       // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
-    // wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device
-    uint32_t* cell_index;      // [3][n]  variable index of each wire cell; n_vars = empty cell / padding row
-    uint32_t* pub_index;       // [n_public]
-    size_t n_vars;
-    Fr* vars;                  // [B][n_vars] values of the resident batch (Montgomery)
-    size_t vars_cap;           // elements
-    plonk_srs* lag_srs;        // Lagrange-basis view of srs (PLONK_PROVER_LAGRANGE_COMMITS), owned by srs
-    size_t resident_b;         // batch size of the witnesses currently resident (run / download must match it)
-    unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
-    hipEvent_t ev_copied, ev_vars_read;  // async upload: the copy stream's H2D is done / the gather kernels have read `vars`
-    bool vars_read_pending;
-    size_t bad_stride;         // values per proof of the last upload that ran the checked conversion: *bad_input / bad_stride owns the bad value
-    bool vars_valid;           // `vars` holds the resident batch (not after plonk_prover_upload_witness)
-    // the witness solver (witness_solve.h; plonk_prover_set_inputs, plonk_prover_upload_inputs)
-    uint8_t* gates_host;       // [5][n] canonical LE: QM, QL, QR, QO, QC as plonk_prover_create was given them
-    uint32_t* cell_host;       // [3][n] host copy of cell_index
-    uint32_t* solve_desc;      // [solve_rows] one descriptor per row (device)
-    uint32_t solve_rows;       // rows the solver walks: up to the last one that is not skipped
-    uint32_t* input_index;     // [n_inputs] the input variables (device)
-    size_t n_inputs;           // 0: no plan (plonk_prover_set_inputs has not been called since the wiring was set)
-    Fr* inputs;                // [B][n_inputs] staging of the uploaded input values (canonical, as copied)
-    uint32_t* solve_bad;       // [B] 0, or 1 + the first row whose check failed
-    size_t inputs_cap;         // proofs `inputs` and `solve_bad` hold
-    bool solve_valid;          // the resident batch came through the solver: solve_bad belongs to it
-    hipEvent_t ev_inputs_read; // async upload: the seed kernel has read `inputs`
-    bool inputs_read_pending;
-    Fq *commit_xy; // [9][B] x||y canonical
-    uint8_t* commit_flags;  // [9][B]
-    ProofState* state;      // [B]
-    ChallengeConsts chal;   // for the challenge reduction in transcript_kernel
+// A device buffer that an upload fills on the copy stream while the previous batch may still be reading it.
+struct Staging {
+    Fr* buf;
+    size_t cap;         // in the owner's units (below)
+    hipEvent_t read;    // recorded behind the last kernel that reads buf (created with the buffer's first allocation)
+    bool read_pending;  // `read` has been recorded: the next asynchronous copy into buf waits for it
 };
+
+struct plonk_prover {
+    // ---- the circuit: set by plonk_prover_create, constant afterwards
+    struct Circuit {
+        plonk_ctx* ctx;
+        plonk_srs* srs;
+        unsigned log_n;
+        size_t n, n_public;
+        Fr g;                // fixed coset offset (Montgomery)
+        Fr w, n_inv, half;   // the n-th root of unity, 1 / n, 1 / 2
+        // The quotient has degree < 3n, so THREE cosets of the n-th roots of unity determine it: x = g mu^r w^j, r < 3 (mu = the
+        // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.
+        Fr* fixed_lag;       // [8][n]   Lagrange values
+        Fr* fixed_coef;      // [8][n]   coefficient forms
+        Fr* fixed_big;       // [8][3][n]  the circuit polynomials on the three cosets
+        Fr* l0_big;          // [3][n]
+        Fr* x_big;           // [3][n]   the points g mu^r w^j
+        Fr* g_pow;           // [3][n]   (g mu^r)^i: the load-side scaling of the size-n transform that evaluates on coset r
+        Fr* ginv_pow;        // [3][n]   (g mu^r)^-i / 2n: the store-side scaling of the inverse transform of coset r (its 1/n folded in)
+        const Fr* roots;     // [n]      w^i (owned by ctx)
+        Fr zh_inv[QCOSETS];  // 1 / (g^n * i^r - 1): Z_H is constant on a coset
+        Fr comb_i, comb_g1, comb_g2;  // quotient_combine_kernel's constants: i = mu^n, 1 / g^n, 1 / g^2n
+        // Public inputs are the only non-zero entries of the PI column (prover.py:57-62): with few of them PI's
+        // coefficient and coset forms are cheaper from the Lagrange basis directly than through two transforms.
+        bool sparse_pi;      // n_public <= PI_SPARSE_MAX
+        Fr* li_big;          // [n_public][4n]  L_i on the coset: (w^i / n) Z_H(x_k) / (x_k - w^i)
+        const Fr* roots_inv; // [n]             w^-i (owned by ctx)
+        ChallengeConsts chal;  // for the challenge reduction in transcript_kernel
+    } circuit;
+    plonk_srs* lag_srs;   // plonk_prover_set_options: Lagrange-basis view of srs (PLONK_PROVER_LAGRANGE_COMMITS), owned by srs
+    unsigned seg_forced;  // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
+    // ---- what the five rounds read and write: per-batch buffers (capacity cap_b proofs; prover.hip: batch_buffers)
+    struct Rounds {
+        size_t cap_b;
+        Fr *wit_lag;   // [4][B][n]  A, B, C, PI   Lagrange
+        Fr *z_lag;     // [B][n]
+        Fr *coef;      // [5][B][n]  Ac, Bc, Cc, PIc, Zc   (coefficient forms; Z last so rounds 1 and 2 fill it in order)
+        Fr *big;       // [5][B][3][n] A, B, C, PI, Z on the three cosets
+        Fr *quot;      // [B][4n]    quotient evaluations on the three cosets, then its 3n coefficients (in place; the last n unused)
+        Fr *num;       // [B][n]     round 2: the grand product's numerator factors (the denominators' go to wz); round 5: W_z's numerator
+        uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
+        Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
+        struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
+        // the segmented scans (prover_scans.h): carries and partial sums of the S segments of every proof, none while S = 1
+        Fr* seg;                   // [scan_scratch_elems(B, S)]
+        size_t seg_cap;            // elements
+    } rounds;
+    // ---- wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device
+    struct Wiring {
+        uint32_t* cell_index;      // [3][n]  variable index of each wire cell; n_vars = empty cell / padding row
+        uint32_t* pub_index;       // [n_public]
+        uint32_t* cell_host;       // [3][n] host copy of cell_index (what plonk_prover_set_inputs plans from)
+        size_t n_vars;
+    } wiring;
+    // ---- intake and staging (prover_intake.h): the batch that is resident, and how its bytes came in
+    struct Intake {
+        size_t resident_b;         // batch size of the witnesses currently resident (run / download must match it)
+        Fr* pub;                   // [B][n_public]   public inputs of the resident batch (Montgomery); a per-batch buffer
+        Staging vars;              // [B][n_vars] values of the resident batch (Montgomery); cap in elements; read by the gathers
+        Staging inputs;            // [B][n_inputs] the uploaded input values (canonical, as copied); cap in proofs; read by the seed
+        bool vars_valid;           // `vars` holds the resident batch (not after plonk_prover_upload_witness)
+        hipEvent_t ev_copied;      // async upload: the copy stream's H2D is done
+        unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
+        size_t bad_stride;         // values per proof of the last upload that ran the checked conversion: *bad_input / bad_stride owns the bad value
+    } intake;
+    // ---- the witness solver (witness_solve.h; plonk_prover_set_inputs, plonk_prover_upload_inputs)
+    struct Solver {
+        uint8_t* gates_host;       // [5][n] canonical LE: QM, QL, QR, QO, QC as plonk_prover_create was given them
+        uint32_t* desc;            // [rows] one descriptor per row (device)
+        uint32_t rows;             // rows the solver walks: up to the last one that is not skipped
+        uint32_t* input_index;     // [n_inputs] the input variables (device)
+        size_t n_inputs;           // 0: no plan (plonk_prover_set_inputs has not been called since the wiring was set)
+        uint32_t* bad;             // [B] 0, or 1 + the first row whose check failed (capacity: intake.inputs.cap proofs)
+        bool valid;                // the resident batch came through the solver: `bad` belongs to it
+    } solver;
+    // ---- results: per-batch buffers like the rounds'
+    struct Results {
+        Fq *commit_xy; // [9][B] x||y canonical
+        uint8_t* commit_flags;  // [9][B]
+        ProofState* state;      // [B]
+    } results;
+};
+static_assert(std::is_trivially_copyable<plonk_prover>::value, "plonk_prover_create zero-fills it with memset: no constructor, no default member initialiser");

@@ -16,43 +16,17 @@
 //   * round 4 evaluates coefficient forms by a blocked Horner; round 5 builds the opening
 //     polynomials in coefficient form (linear combination + synthetic division by X - z), so the
 //     reference's ~15 further coset extensions and its 4n-point divisions never happen.
+#include <assert.h>
 #include <string.h>
+
+#include <array>
 
 #include "prover.h"
 #include "g1_codec.h"
 #include "prover_scans.h"  // rounds 2, 4 and 5: the grand product, the evaluations, the divisions — kernels and launchers
-#include "witness_solve.h"  // the variables of a batch from its input values: the plan, the solver's kernels
+#include "prover_intake.h"  // a batch from the caller's bytes to resident witnesses: the uploads, the wiring, the witness solver
 
 // ------------------------------------------------------------------------------------------------
-// witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
-__global__ void pi_fill_kernel(const Fr* pub, size_t n_public, size_t n, size_t B, Fr* pi) {
-    const size_t total = B * n;
-    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = gI / n, i = gI - b * n;
-        Fr v = fp_zero<FrParams>();
-        if (i < n_public) v = fp_neg(fp_load(pub + b * n_public + i));
-        fp_store(pi + gI, v);
-    }
-}
-
-// prover.py:94-103 on the device: A[i], B[i], C[i] = witness[wires[i].L / R / O], witness[None] = 0, zero padded to n.
-// vars = [B][V] variable values; cell[3][n] = variable index of each wire cell (V: empty); out = wit_lag [3][B][n].
-__global__ void witness_scatter_kernel(const Fr* vars, const uint32_t* cell, size_t V, size_t n, size_t B, Fr* out) {
-    const size_t total = 3 * B * n;
-    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
-        const size_t j = gI / (B * n), r = gI - j * B * n, b = r / n, i = r - b * n;
-        const uint32_t idx = cell[j * n + i];
-        fp_store(out + gI, idx < V ? fp_load(vars + b * V + idx) : fp_zero<FrParams>());
-    }
-}
-__global__ void public_gather_kernel(const Fr* vars, const uint32_t* pub_index, size_t V, size_t l, size_t B, Fr* pub) {
-    const size_t total = B * l;
-    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = gI / l, k = gI - b * l;
-        fp_store(pub + gI, fp_load(vars + b * V + pub_index[k]));
-    }
-}
-
 // Sparse public inputs.  PI = sum_{i < l} (-pub_i) L_i with L_i the Lagrange basis of the n-th roots of unity:
 //   coefficient j of L_i is  w^(-ij) / n            (an inverse DFT of a unit vector)
 //   L_i(x) = (w^i / n) (x^n - 1) / (x - w^i)        (li_big holds it on the coset points: [3][n] coset-major)
@@ -377,63 +351,69 @@ __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes,
 
 // S of a prover's batch: PLONK_PROVER_SEGMENTS_LOG2 where it was set, the automatic rule otherwise
 static unsigned prover_segments(const plonk_prover* p, size_t B) {
-    return p->seg_forced ? 1u << (p->seg_forced - 1) : prover_plan_segments(device_cus(p->ctx->device), p->log_n, B);
+    return p->seg_forced ? 1u << (p->seg_forced - 1) : prover_plan_segments(device_cus(p->circuit.ctx->device), p->circuit.log_n, B);
+}
+
+// The per-batch buffers, once: what ensure_batch allocates, free_batch frees and the out-of-memory message adds up.  Per proof a buffer
+// holds n_vectors Fr vectors of n elements and `bytes` more; `extra` bytes once.
+struct BatchBuffer { void** slot; size_t n_vectors, bytes, extra; };
+#define BATCH_N_VECTORS 32  // 32 n-vectors of 32 bytes per proof: the figure of the out-of-memory message
+static std::array<BatchBuffer, 13> batch_buffers(plonk_prover* p) {
+    plonk_prover::Rounds& r = p->rounds;
+    plonk_prover::Results& o = p->results;
+    const size_t e = sizeof(Fr);
+    return {{{(void**)&r.wit_lag, 4}, {(void**)&r.z_lag, 1}, {(void**)&r.coef, 5}, {(void**)&r.big, 5 * QCOSETS}, {(void**)&r.quot, 4},
+             {(void**)&r.num, 1}, {(void**)&r.wz, 2}, {(void**)&r.closes, 0, 2 * sizeof(uint32_t)}, {(void**)&r.lin_w, 0, sizeof(LinWeights)},
+             {(void**)&o.commit_xy, 0, PROOF_POINTS * 2 * sizeof(Fq)}, {(void**)&o.commit_flags, 0, PROOF_POINTS},
+             {(void**)&o.state, 0, sizeof(ProofState)}, {(void**)&p->intake.pub, 0, p->circuit.n_public * e, e}}};
 }
 
 static void free_batch(plonk_prover* p) {
-    dev_free_all({(void**)&p->seg});
-    p->seg_cap = 0;
-    dev_free_all({(void**)&p->wit_lag, (void**)&p->z_lag, (void**)&p->coef, (void**)&p->big, (void**)&p->quot, (void**)&p->num, (void**)&p->closes,
-                  (void**)&p->wz, (void**)&p->commit_xy, (void**)&p->commit_flags, (void**)&p->state, (void**)&p->pub, (void**)&p->lin_w,
-                  (void**)&p->vars});
-    p->vars_cap = 0;
-    p->resident_b = 0;
-    p->cap_b = 0;
+    for (const BatchBuffer& b : batch_buffers(p)) dev_free_all({b.slot});
+    dev_free_all({(void**)&p->rounds.seg, (void**)&p->intake.vars.buf});  // sized by the batch too: they make room for a larger one
+    p->rounds.seg_cap = p->intake.vars.cap = p->intake.resident_b = p->rounds.cap_b = 0;
 }
 
 // the carries and partial sums of the segmented scans (prover_scans.h: scan_scratch_elems)
 static int ensure_segments(plonk_prover* p, size_t B) {
     const size_t need = scan_scratch_elems(B, prover_segments(p, B));
-    if (need <= p->seg_cap) return PLONK_OK;
-    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
-    dev_free_all({(void**)&p->seg});
-    p->seg_cap = 0;
-    PLONK_TRY(dev_alloc((void**)&p->seg, need * sizeof(Fr)));
-    p->seg_cap = need;
-    return PLONK_OK;
-}
-
-static int alloc_batch(plonk_prover* p, size_t B) {
-    const size_t n = p->n, e = sizeof(Fr);
-    PLONK_TRY(dev_alloc((void**)&p->wit_lag, 4 * B * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->z_lag, B * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->coef, 5 * B * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->big, 5 * B * QCOSETS * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->quot, B * 4 * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->num, B * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->closes, 2 * B * sizeof(uint32_t)));
-    PLONK_TRY(dev_alloc((void**)&p->wz, 2 * B * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->commit_xy, PROOF_POINTS * B * 2 * sizeof(Fq)));
-    PLONK_TRY(dev_alloc((void**)&p->commit_flags, PROOF_POINTS * B));
-    PLONK_TRY(dev_alloc((void**)&p->state, B * sizeof(ProofState)));
-    PLONK_TRY(dev_alloc((void**)&p->pub, (B * p->n_public + 1) * e));
-    PLONK_TRY(dev_alloc((void**)&p->lin_w, B * sizeof(LinWeights)));
-    return PLONK_OK;
+    return dev_grow(p->circuit.ctx->stream, &p->rounds.seg_cap, need, {{(void**)&p->rounds.seg, need * sizeof(Fr)}});
 }
 
 static int ensure_batch(plonk_prover* p, size_t B) {
-    if (B <= p->cap_b) return ensure_segments(p, B);
-    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
+    if (B <= p->rounds.cap_b) return ensure_segments(p, B);
+    PLONK_CHECK_HIP(hipStreamSynchronize(p->circuit.ctx->stream));
     free_batch(p);
-    const int rc = alloc_batch(p, B);
-    if (rc != PLONK_OK) {  // 32 n-vectors of 32 bytes per proof: 4 + 1 + 5 + 15 + 4 + 1 + 2
+    int rc = PLONK_OK;
+    size_t vectors = 0;
+    for (const BatchBuffer& b : batch_buffers(p)) {
+        if (rc == PLONK_OK) rc = dev_alloc(b.slot, B * (b.n_vectors * p->circuit.n * sizeof(Fr) + b.bytes) + b.extra);
+        vectors += b.n_vectors;
+    }
+    assert(vectors == BATCH_N_VECTORS);
+    if (rc != PLONK_OK) {
         free_batch(p);
         if (rc == PLONK_ERR_NOMEM)
-            plonk_set_error("a batch of %zu proofs of group_order %zu needs %zu bytes of device memory", B, p->n, 32 * B * p->n * sizeof(Fr));
+            plonk_set_error("a batch of %zu proofs of group_order %zu needs %zu bytes of device memory", B, p->circuit.n,
+                            BATCH_N_VECTORS * B * p->circuit.n * sizeof(Fr));
         return rc;
     }
-    p->cap_b = B;
+    p->rounds.cap_b = B;
     return ensure_segments(p, B);
+}
+
+// One transcript round of every proof: round 0 opens the transcripts, round r absorbs what round r of the prover produced.
+static void transcript_round(plonk_prover* p, size_t B, int round) {
+    PLONK_LAUNCH(transcript_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, p->circuit.ctx->stream, round, p->results.state, B,
+                 (const Fq*)p->results.commit_xy, (const uint8_t*)p->results.commit_flags, p->circuit.chal);
+}
+
+// `count` x B commitments into the proof records' points from `first_point` on: of the Lagrange values under the Lagrange-basis
+// SRS where PLONK_PROVER_LAGRANGE_COMMITS is set (the same points), of the coefficient forms otherwise
+static int commit(plonk_prover* p, size_t B, const Fr* lag, const Fr* coef, size_t count, size_t first_point) {
+    const plonk_prover::Circuit& c = p->circuit;
+    return msm_run_device(c.ctx, p->lag_srs ? p->lag_srs : c.srs, p->lag_srs ? lag : coef, c.n, count * B, c.n, p->results.commit_xy + 2 * first_point * B,
+                          p->results.commit_flags + first_point * B);
 }
 
 static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32, size_t n_public);
@@ -465,70 +445,69 @@ int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const ui
 static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
                        size_t n_public) {
     const size_t n = (size_t)1 << log_n;
-    p->ctx = ctx;
-    p->srs = srs;
-    p->log_n = log_n;
-    p->n = n;
-    p->n_public = n_public;
-    p->chal = challenge_consts();
-    p->g = host_fr_u64(5);  // multiplicative generator (curve.py:5): g^(4n) != 1, so Z_H != 0 on the coset
-    p->w = host_root_of_unity(log_n, false);
-    p->n_inv = fp_inv(host_fr_u64((uint64_t)n));
-    p->half = fp_inv(host_fr_u64(2));
+    plonk_prover::Circuit& c = p->circuit;
+    c.ctx = ctx;
+    c.srs = srs;
+    c.log_n = log_n;
+    c.n = n;
+    c.n_public = n_public;
+    c.chal = challenge_consts();
+    c.g = host_fr_u64(5);  // multiplicative generator (curve.py:5): g^(4n) != 1, so Z_H != 0 on the coset
+    c.w = host_root_of_unity(log_n, false);
+    c.n_inv = fp_inv(host_fr_u64((uint64_t)n));
+    c.half = fp_inv(host_fr_u64(2));
     const size_t e = sizeof(Fr);
-    PLONK_TRY(dev_alloc((void**)&p->fixed_lag, 8 * n * e));
-    PLONK_TRY(dev_alloc((void**)&p->fixed_coef, 8 * n * e));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_lag, 8 * n * e));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_coef, 8 * n * e));
     const size_t n3 = QCOSETS * n;
-    PLONK_TRY(dev_alloc((void**)&p->fixed_big, 8 * n3 * e));
-    PLONK_TRY(dev_alloc((void**)&p->l0_big, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&p->x_big, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&p->g_pow, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&p->ginv_pow, n3 * e));
-    PLONK_TRY(plonk_fr_upload(ctx, p->fixed_lag, selectors_le32, 8 * n));
-    p->gates_host = (uint8_t*)malloc(5 * n * 32);  // QM .. QC as given: what plonk_prover_set_inputs classifies
-    PLONK_REQUIRE(p->gates_host, PLONK_ERR_NOMEM, "out of host memory");
-    memcpy(p->gates_host, selectors_le32, 5 * n * 32);
-    PLONK_TRY(ntt_get_roots(ctx, log_n, false, &p->roots));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_big, 8 * n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.l0_big, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.x_big, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.g_pow, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.ginv_pow, n3 * e));
+    PLONK_TRY(plonk_fr_upload(ctx, c.fixed_lag, selectors_le32, 8 * n));
+    PLONK_TRY(intake_init(p, selectors_le32));
+    PLONK_TRY(ntt_get_roots(ctx, log_n, false, &c.roots));
     const Fr one = fp_one<FrParams>();
     const Fr mu = host_root_of_unity(log_n + 2, false);
-    Fr base = p->g;  // g mu^r
+    Fr base = c.g;  // g mu^r
     for (unsigned r = 0; r < QCOSETS; r++) {
-        PLONK_TRY(k_fr_powers(ctx, base, one, p->g_pow + r * n, n));
-        PLONK_TRY(k_fr_powers(ctx, fp_inv(base), fp_mul(p->half, p->n_inv), p->ginv_pow + r * n, n));
-        PLONK_TRY(k_fr_powers(ctx, p->w, base, p->x_big + r * n, n));
+        PLONK_TRY(k_fr_powers(ctx, base, one, c.g_pow + r * n, n));
+        PLONK_TRY(k_fr_powers(ctx, fp_inv(base), fp_mul(c.half, c.n_inv), c.ginv_pow + r * n, n));
+        PLONK_TRY(k_fr_powers(ctx, c.w, base, c.x_big + r * n, n));
         base = fp_mul(base, mu);
     }
     // coefficient forms of the 8 circuit polynomials, and their values on the three cosets: P(g mu^r w^j) is the size-n
     // transform of c_i (g mu^r)^i
-    PLONK_TRY(ntt_run(ctx, p->fixed_lag, p->fixed_coef, log_n, true, 8, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(ntt_run(ctx, c.fixed_lag, c.fixed_coef, log_n, true, 8, n, n, n, nullptr, nullptr, true));
     const NttFan fan{QCOSETS, 0u, (unsigned)n, (unsigned)n};
-    PLONK_TRY(ntt_run(ctx, p->fixed_coef, p->fixed_big, log_n, false, 8, n, n, n3, p->g_pow, nullptr, false, &fan));
+    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8, n, n, n3, c.g_pow, nullptr, false, &fan));
     // L0: Lagrange vector e_0 has coefficient form (1/n, 1/n, ...)          prover.py:184-186
     void* tmpv;
     PLONK_TRY(ctx_scratch(ctx, 2, n * e, &tmpv));  // context-owned scratch: nothing to leak on an error path
     Fr* tmp = (Fr*)tmpv;
-    PLONK_TRY(k_fr_powers(ctx, one, p->n_inv, tmp, n));
-    PLONK_TRY(ntt_run(ctx, tmp, p->l0_big, log_n, false, 1, n, n, n3, p->g_pow, nullptr, false, &fan));
+    PLONK_TRY(k_fr_powers(ctx, one, c.n_inv, tmp, n));
+    PLONK_TRY(ntt_run(ctx, tmp, c.l0_big, log_n, false, 1, n, n, n3, c.g_pow, nullptr, false, &fan));
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     // Z_H on coset r is the constant (g mu^r)^n - 1 = g^n i^r - 1, i = mu^n            prover.py:178
-    Fr gn = p->g;
+    Fr gn = c.g;
     for (unsigned i = 0; i < log_n; i++) gn = fp_sqr(gn);
     Fr i4 = host_root_of_unity(2, false), cur = gn;
     Zh4 zh4;
     for (int k = 0; k < 4; k++) {
         zh4.v[k] = fp_sub(cur, one);
-        if (k < QCOSETS) p->zh_inv[k] = fp_inv(zh4.v[k]);
+        if (k < QCOSETS) c.zh_inv[k] = fp_inv(zh4.v[k]);
         cur = fp_mul(cur, i4);
     }
-    p->comb_i = i4;
-    p->comb_g1 = fp_inv(gn);
-    p->comb_g2 = fp_mul(fp_sqr(p->comb_g1), p->half);
-    p->sparse_pi = n_public <= PI_SPARSE_MAX;
-    if (p->sparse_pi && n_public) {
-        PLONK_TRY(ntt_get_roots(ctx, log_n, true, &p->roots_inv));
-        PLONK_TRY(dev_alloc((void**)&p->li_big, n_public * n3 * e));
-        PLONK_LAUNCH(li_coset_kernel, grid1(n_public * n3), dim3(256), 0, ctx->stream, (const Fr*)p->x_big, p->roots, n3, n, n_public,
-                     zh4, p->n_inv, p->li_big);
+    c.comb_i = i4;
+    c.comb_g1 = fp_inv(gn);
+    c.comb_g2 = fp_mul(fp_sqr(c.comb_g1), c.half);
+    c.sparse_pi = n_public <= PI_SPARSE_MAX;
+    if (c.sparse_pi && n_public) {
+        PLONK_TRY(ntt_get_roots(ctx, log_n, true, &c.roots_inv));
+        PLONK_TRY(dev_alloc((void**)&c.li_big, n_public * n3 * e));
+        PLONK_LAUNCH(li_coset_kernel, grid1(n_public * n3), dim3(256), 0, ctx->stream, (const Fr*)c.x_big, c.roots, n3, n, n_public,
+                     zh4, c.n_inv, c.li_big);
         PLONK_CHECK_HIP(hipGetLastError());
         PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
@@ -539,288 +518,28 @@ extern "C" {
 
 int plonk_prover_set_options(plonk_prover* p, unsigned flags) {
     PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK)), PLONK_ERR_ARG, "unknown prover option bits %#x", flags);
-    PLONK_ENTER(p->ctx);
+    PLONK_ENTER(p->circuit.ctx);
     const unsigned seg = (flags & PLONK_PROVER_SEGMENTS_MASK) >> 8;  // k + 1, 0 = automatic
-    PLONK_REQUIRE(seg <= 9 && (!seg || (p->n >> (seg - 1)) >= 16), PLONK_ERR_ARG,
-                  "2^%u segments: at most 256, of at least 16 rows each (group_order %zu)", seg ? seg - 1 : 0, p->n);
+    PLONK_REQUIRE(seg <= 9 && (!seg || (p->circuit.n >> (seg - 1)) >= 16), PLONK_ERR_ARG,
+                  "2^%u segments: at most 256, of at least 16 rows each (group_order %zu)", seg ? seg - 1 : 0, p->circuit.n);
     p->seg_forced = seg;
     p->lag_srs = nullptr;
-    if (flags & PLONK_PROVER_LAGRANGE_COMMITS) PLONK_TRY(msm_lagrange_srs(p->ctx, p->srs, p->log_n, &p->lag_srs));
+    if (flags & PLONK_PROVER_LAGRANGE_COMMITS) PLONK_TRY(msm_lagrange_srs(p->circuit.ctx, p->circuit.srs, p->circuit.log_n, &p->lag_srs));
     return PLONK_OK;
 }
 
 int plonk_prover_destroy(plonk_prover* p) {
     if (!p) return PLONK_OK;
-    if (p->ctx) {
-        plonk_use_device(p->ctx->device);
-        hipStreamSynchronize(p->ctx->stream);
+    plonk_prover::Circuit& c = p->circuit;
+    if (c.ctx) {
+        plonk_use_device(c.ctx->device);
+        hipStreamSynchronize(c.ctx->stream);
     }
     free_batch(p);
-    dev_free_all({(void**)&p->fixed_lag, (void**)&p->fixed_coef, (void**)&p->fixed_big, (void**)&p->l0_big, (void**)&p->x_big, (void**)&p->g_pow,
-                  (void**)&p->ginv_pow, (void**)&p->li_big, (void**)&p->cell_index, (void**)&p->pub_index, (void**)&p->solve_desc,
-                  (void**)&p->input_index, (void**)&p->inputs, (void**)&p->solve_bad});
-    free(p->gates_host);
-    free(p->cell_host);
-    if (p->ev_inputs_read) hipEventDestroy(p->ev_inputs_read);
-    if (p->bad_input) {
-        hipFree(p->bad_input);
-        hipEventDestroy(p->ev_copied);
-        hipEventDestroy(p->ev_vars_read);
-    }
+    dev_free_all({(void**)&c.fixed_lag, (void**)&c.fixed_coef, (void**)&c.fixed_big, (void**)&c.l0_big, (void**)&c.x_big, (void**)&c.g_pow,
+                  (void**)&c.ginv_pow, (void**)&c.li_big});
+    intake_destroy(p);
     delete p;
-    return PLONK_OK;
-}
-
-// the PI column of the B uploaded witnesses, wit_lag[3]: -public inputs, then zeros (the sparse form is built from `pub` in round 1)
-static int fill_pi_column(plonk_prover* p, size_t B) {
-    Fr* pi = p->wit_lag + 3 * B * p->n;
-    if (!p->n_public) PLONK_CHECK_HIP(hipMemsetAsync(pi, 0, B * p->n * sizeof(Fr), p->ctx->stream));
-    else if (!p->sparse_pi)
-        PLONK_LAUNCH(pi_fill_kernel, grid1(B * p->n), dim3(256), 0, p->ctx->stream, (const Fr*)p->pub, p->n_public, p->n, B, pi);
-    PLONK_CHECK_HIP(hipGetLastError());
-    return PLONK_OK;
-}
-
-// witness columns [3][B][n] (A, B, C) and public inputs [B][n_public], canonical LE
-int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t B) {
-    PLONK_REQUIRE(p && abc_le32 && B && (public_le32 || !p->n_public), PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
-    PLONK_TRY(ensure_batch(p, B));
-    plonk_ctx* ctx = p->ctx;
-    // a verdict left by an earlier asynchronous upload does not belong to this batch (plonk_fr_upload reports its own
-    // non-canonical values synchronously, as PLONK_ERR_ARG)
-    if (p->bad_input) PLONK_CHECK_HIP(hipMemsetAsync(p->bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
-    PLONK_TRY(plonk_fr_upload(ctx, p->wit_lag, abc_le32, 3 * B * p->n));
-    if (p->n_public) PLONK_TRY(plonk_fr_upload(ctx, p->pub, public_le32, B * p->n_public));
-    PLONK_TRY(fill_pi_column(p, B));
-    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    p->resident_b = B;
-    p->vars_valid = p->solve_valid = false;
-    return PLONK_OK;
-}
-
-// cell_index[3][n]: variable index carried by each wire cell (column L/R/O, row), n_vars for an empty cell or a
-// padding row; public_index[n_public]: the public variables, in the order of the public rows (prover.py:57-62).
-int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars) {
-    PLONK_REQUIRE(p && cell_index && n_vars && (public_index || !p->n_public), PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
-    for (size_t k = 0; k < 3 * p->n; k++)
-        PLONK_REQUIRE(cell_index[k] <= n_vars, PLONK_ERR_ARG, "wire cell %zu names variable %u of %zu", k, cell_index[k], n_vars);
-    for (size_t k = 0; k < p->n_public; k++)
-        PLONK_REQUIRE(public_index[k] < n_vars, PLONK_ERR_ARG, "public input %zu names variable %u of %zu", k, public_index[k], n_vars);
-    if (!p->cell_index) PLONK_TRY(dev_alloc((void**)&p->cell_index, 3 * p->n * sizeof(uint32_t)));
-    if (!p->pub_index) PLONK_TRY(dev_alloc((void**)&p->pub_index, (p->n_public + 1) * sizeof(uint32_t)));
-    PLONK_CHECK_HIP(hipMemcpyAsync(p->cell_index, cell_index, 3 * p->n * sizeof(uint32_t), hipMemcpyHostToDevice, p->ctx->stream));
-    if (p->n_public)
-        PLONK_CHECK_HIP(hipMemcpyAsync(p->pub_index, public_index, p->n_public * sizeof(uint32_t), hipMemcpyHostToDevice, p->ctx->stream));
-    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
-    if (!p->cell_host) p->cell_host = (uint32_t*)malloc(3 * p->n * sizeof(uint32_t));
-    PLONK_REQUIRE(p->cell_host, PLONK_ERR_NOMEM, "out of host memory");
-    memcpy(p->cell_host, cell_index, 3 * p->n * sizeof(uint32_t));
-    p->n_vars = n_vars;
-    p->n_inputs = 0;  // a plan belongs to the wiring it was built from
-    p->vars_valid = false;
-    return PLONK_OK;
-}
-
-// values of the n_vars variables of each witness, [B][n_vars] canonical LE (n_vars * 32 bytes per proof instead of
-// 3 * n * 32): the wire columns and the public inputs are gathered from them on the device (prover.py:94-103, 57-62).
-// async: the host-to-device copy goes to the context's copy stream (it overlaps whatever the compute stream is running —
-// another prover's rounds, or this prover's previous batch, which no longer reads `vars`), the conversion and the gather
-// follow on the compute stream behind an event, nothing waits on the host; the canonical-range verdict stays on the
-// device and comes back as PROVER_ST_BAD_INPUT of plonk_prover_download.  The caller keeps vars_le32 alive (and, for a copy
-// that really is asynchronous, in pinned memory: plonk_host_alloc) until the batch has been downloaded.
-// the per-batch buffers, `vars` [B][n_vars] and what the checked conversion and the asynchronous uploads need
-static int ensure_vars(plonk_prover* p, size_t B) {
-    PLONK_TRY(ensure_batch(p, B));
-    plonk_ctx* ctx = p->ctx;
-    const size_t V = p->n_vars;
-    if (p->vars_cap < B * V) {
-        PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        dev_free_all({(void**)&p->vars});
-        p->vars_cap = 0;
-        PLONK_TRY(dev_alloc((void**)&p->vars, B * V * sizeof(Fr)));
-        p->vars_cap = B * V;
-    }
-    if (!p->bad_input) {
-        PLONK_TRY(dev_alloc((void**)&p->bad_input, sizeof(unsigned long long)));
-        PLONK_CHECK_HIP(hipEventCreate(&p->ev_copied));
-        PLONK_CHECK_HIP(hipEventCreate(&p->ev_vars_read));
-    }
-    return PLONK_OK;
-}
-
-// the wire columns, the public inputs and the PI column from `vars`; ev_vars_read marks the last read of `vars`
-static int gather_from_vars(plonk_prover* p, size_t B) {
-    plonk_ctx* ctx = p->ctx;
-    const size_t n = p->n, V = p->n_vars;
-    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, ctx->stream, (const Fr*)p->vars, (const uint32_t*)p->cell_index, V,
-                 n, B, p->wit_lag);
-    if (p->n_public)
-        PLONK_LAUNCH(public_gather_kernel, grid1(B * p->n_public), dim3(256), 0, ctx->stream, (const Fr*)p->vars,
-                     (const uint32_t*)p->pub_index, V, p->n_public, B, p->pub);
-    PLONK_TRY(fill_pi_column(p, B));
-    PLONK_CHECK_HIP(hipEventRecord(p->ev_vars_read, ctx->stream));
-    p->vars_read_pending = true;
-    return PLONK_OK;
-}
-
-static int prover_upload_vars(plonk_prover* p, const uint8_t* vars_le32, size_t B, bool async) {
-    PLONK_REQUIRE(p && vars_le32 && B, PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
-    PLONK_REQUIRE(p->n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
-    PLONK_TRY(ensure_vars(p, B));
-    plonk_ctx* ctx = p->ctx;
-    const size_t V = p->n_vars;
-    p->resident_b = 0;  // until the new batch is in place (a failed upload leaves no batch to run)
-    p->vars_valid = p->solve_valid = false;
-    p->bad_stride = V;
-    if (async) {
-        PLONK_TRY(ctx_copy_stream(ctx));
-        if (p->vars_read_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->copy_stream, p->ev_vars_read, 0));  // the previous gather has read vars
-        PLONK_CHECK_HIP(hipMemcpyAsync(p->vars, vars_le32, B * V * sizeof(Fr), hipMemcpyHostToDevice, ctx->copy_stream));
-        PLONK_CHECK_HIP(hipEventRecord(p->ev_copied, ctx->copy_stream));
-        PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, p->ev_copied, 0));
-        PLONK_TRY(k_fr_to_mont_checked(ctx, p->vars, B * V, p->bad_input));
-    } else {
-        PLONK_CHECK_HIP(hipMemsetAsync(p->bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
-        PLONK_TRY(plonk_fr_upload(ctx, p->vars, vars_le32, B * V));  // waits, and reports a non-canonical value as PLONK_ERR_ARG
-    }
-    PLONK_TRY(gather_from_vars(p, B));
-    if (!async) PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    p->resident_b = B;
-    p->vars_valid = true;
-    return PLONK_OK;
-}
-
-int plonk_prover_upload_variables(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload_vars(p, vars_le32, B, false); }
-int plonk_prover_upload_variables_async(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload_vars(p, vars_le32, B, true); }
-
-// ---- the witness solver (witness_solve.h) ----------------------------------------------------------------------------------
-// The circuit's inputs: the variables a batch will give values for.  Builds the solver's plan from the gate columns
-// plonk_prover_create was given and the wiring; a refusal that names a variable (one that no row assigns before it is read, or
-// at all) sets *out_missing_var to it, any other sets it to 0xffffffff.
-int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t n_inputs, uint32_t* out_missing_var) {
-    PLONK_REQUIRE(p && input_index && n_inputs && out_missing_var, PLONK_ERR_ARG, "bad argument");
-    *out_missing_var = SOLVE_NO_VARIABLE;
-    PLONK_ENTER(p->ctx);
-    PLONK_REQUIRE(p->n_vars && p->cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
-    plonk_ctx* ctx = p->ctx;
-    std::vector<uint32_t> desc;
-    PLONK_TRY(solve_plan_build(p->gates_host, p->cell_host, p->n, p->n_vars, input_index, n_inputs, desc, out_missing_var));
-    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // a batch in flight still walks the old plan
-    p->n_inputs = 0;
-    p->resident_b = 0;
-    dev_free_all({(void**)&p->solve_desc, (void**)&p->input_index, (void**)&p->inputs, (void**)&p->solve_bad});
-    p->inputs_cap = 0;
-    PLONK_TRY(dev_alloc((void**)&p->solve_desc, desc.size() * sizeof(uint32_t)));
-    PLONK_TRY(dev_alloc((void**)&p->input_index, n_inputs * sizeof(uint32_t)));
-    if (!desc.empty())
-        PLONK_CHECK_HIP(hipMemcpyAsync(p->solve_desc, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    PLONK_CHECK_HIP(hipMemcpyAsync(p->input_index, input_index, n_inputs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    p->solve_rows = (uint32_t)desc.size();
-    p->n_inputs = n_inputs;
-    return PLONK_OK;
-}
-
-// values of the n_inputs input variables of each witness, [B][n_inputs] canonical LE: seed -> solve -> the gathers of
-// plonk_prover_upload_variables.  async: the contract of plonk_prover_upload_variables_async — the copy on the copy stream behind
-// the previous batch's last read of the staging buffer, everything else behind an event on the compute stream, no host wait, a
-// value that is not below r reported as PROVER_ST_BAD_INPUT.
-static int prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B, bool async) {
-    PLONK_REQUIRE(p && inputs_le32 && B, PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
-    PLONK_REQUIRE(p->n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
-    PLONK_REQUIRE(p->n_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
-    PLONK_TRY(ensure_vars(p, B));
-    plonk_ctx* ctx = p->ctx;
-    const size_t V = p->n_vars, K = p->n_inputs;
-    if (p->inputs_cap < B) {
-        PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        dev_free_all({(void**)&p->inputs, (void**)&p->solve_bad});
-        p->inputs_cap = 0;
-        PLONK_TRY(dev_alloc((void**)&p->inputs, B * K * sizeof(Fr)));
-        PLONK_TRY(dev_alloc((void**)&p->solve_bad, B * sizeof(uint32_t)));
-        p->inputs_cap = B;
-    }
-    if (!p->ev_inputs_read) PLONK_CHECK_HIP(hipEventCreate(&p->ev_inputs_read));
-    p->resident_b = 0;  // until the new batch is in place
-    p->vars_valid = p->solve_valid = false;
-    p->bad_stride = K;
-    hipStream_t s = ctx->stream;
-    if (async) {
-        PLONK_TRY(ctx_copy_stream(ctx));
-        if (p->inputs_read_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->copy_stream, p->ev_inputs_read, 0));  // the previous seed has read inputs
-        PLONK_CHECK_HIP(hipMemcpyAsync(p->inputs, inputs_le32, B * K * sizeof(Fr), hipMemcpyHostToDevice, ctx->copy_stream));
-        PLONK_CHECK_HIP(hipEventRecord(p->ev_copied, ctx->copy_stream));
-        PLONK_CHECK_HIP(hipStreamWaitEvent(s, p->ev_copied, 0));
-    } else {
-        PLONK_CHECK_HIP(hipMemcpyAsync(p->inputs, inputs_le32, B * K * sizeof(Fr), hipMemcpyHostToDevice, s));
-    }
-    PLONK_CHECK_HIP(hipMemsetAsync(p->bad_input, 0xff, sizeof(unsigned long long), s));
-    // (the solver writes `vars` in place: on the compute stream it is behind the previous batch's gathers, the only readers)
-    PLONK_LAUNCH(witness_seed_kernel, grid1(B * K), dim3(256), 0, s, (const Fr*)p->inputs, (const uint32_t*)p->input_index, K, V, B, p->vars,
-                 p->bad_input, p->solve_bad);
-    PLONK_CHECK_HIP(hipEventRecord(p->ev_inputs_read, s));
-    p->inputs_read_pending = true;
-    PLONK_TRY(prof_begin(ctx, "witness_solve", 32.0 * (double)V * (double)B));
-    PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, p->vars, (const uint32_t*)p->solve_desc,
-                 (const uint32_t*)p->cell_index, (const Fr*)p->fixed_lag, V, p->n, p->solve_rows, B, p->solve_bad);
-    PLONK_TRY(prof_end(ctx));
-    PLONK_TRY(gather_from_vars(p, B));
-    if (!async) {
-        unsigned long long first_bad = 0;
-        PLONK_CHECK_HIP(hipMemcpyAsync(&first_bad, p->bad_input, sizeof first_bad, hipMemcpyDeviceToHost, s));
-        PLONK_CHECK_HIP(hipStreamSynchronize(s));
-        PLONK_REQUIRE(first_bad == ~0ull, PLONK_ERR_ARG, "input %llu of proof %llu is not a canonical Fr value (>= r)", first_bad % K, first_bad / K);
-    }
-    p->resident_b = B;
-    p->vars_valid = p->solve_valid = true;
-    return PLONK_OK;
-}
-int plonk_prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload_inputs(p, inputs_le32, B, false); }
-int plonk_prover_upload_inputs_async(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload_inputs(p, inputs_le32, B, true); }
-
-// [B][k] canonical LE values of the variables var_index[0 .. k) of the resident batch (var_index == NULL: all n_vars, k
-// ignored), after either kind of variable upload: what the solver computed — a public input among it — for the verifier
-int plonk_prover_download_variables(plonk_prover* p, size_t B, const uint32_t* var_index, size_t k, uint8_t* out_le32) {
-    PLONK_REQUIRE(p && B && out_le32 && (k || !var_index), PLONK_ERR_ARG, "bad argument");
-    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "download_variables: batch %zu, but %zu witnesses are resident", B, p->resident_b);
-    PLONK_REQUIRE(p->vars_valid, PLONK_ERR_STATE, "the resident batch was uploaded as wire columns: it has no variable values");
-    PLONK_ENTER(p->ctx);
-    plonk_ctx* ctx = p->ctx;
-    const size_t V = p->n_vars;
-    if (!var_index) k = V;
-    for (size_t j = 0; var_index && j < k; j++)
-        PLONK_REQUIRE(var_index[j] < V, PLONK_ERR_ARG, "index %zu names variable %u of %zu", j, var_index[j], V);
-    void* tmp;
-    PLONK_TRY(ctx_scratch(ctx, 3, B * k * sizeof(Fr) + k * sizeof(uint32_t), &tmp));
-    Fr* vals = (Fr*)tmp;
-    uint32_t* d_index = nullptr;
-    if (var_index) {
-        d_index = reinterpret_cast<uint32_t*>(vals + B * k);
-        PLONK_CHECK_HIP(hipMemcpyAsync(d_index, var_index, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    PLONK_LAUNCH(variable_gather_kernel, grid1(B * k), dim3(256), 0, ctx->stream, (const Fr*)p->vars, (const uint32_t*)d_index, V, k, B, vals);
-    PLONK_CHECK_HIP(hipGetLastError());
-    PLONK_CHECK_HIP(hipMemcpyAsync(out_le32, vals, B * k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    return PLONK_OK;
-}
-
-// per proof of the resident batch, 0 or 1 + the first row whose check failed (PROVER_ST_ASSERT); a batch that did not come
-// through the solver has none
-int plonk_prover_solve_failures(plonk_prover* p, size_t B, uint32_t* out_rows) {
-    PLONK_REQUIRE(p && B && out_rows, PLONK_ERR_ARG, "bad argument");
-    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "solve_failures: batch %zu, but %zu witnesses are resident", B, p->resident_b);
-    PLONK_ENTER(p->ctx);
-    if (!p->solve_valid) {
-        memset(out_rows, 0, B * sizeof(uint32_t));
-        return PLONK_OK;
-    }
-    PLONK_CHECK_HIP(hipMemcpyAsync(out_rows, p->solve_bad, B * sizeof(uint32_t), hipMemcpyDeviceToHost, p->ctx->stream));
-    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
     return PLONK_OK;
 }
 
@@ -828,102 +547,90 @@ int plonk_prover_solve_failures(plonk_prover* p, size_t B, uint32_t* out_rows) {
 int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_REQUIRE(p && B, PLONK_ERR_ARG, "bad argument");
     // every buffer is laid out [k][B][n] with the B of the upload: another B would read the wrong strides
-    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "run: batch %zu, but %zu witnesses are resident", B, p->resident_b);
-    PLONK_ENTER(p->ctx);
-    plonk_ctx* ctx = p->ctx;
-    const size_t n = p->n, n4 = 4 * n;
-    const unsigned log_n = p->log_n;
-    const unsigned tb = (unsigned)((B + 63) / 64), tg = (unsigned)((B + 1) / 2);
+    PLONK_REQUIRE(B == p->intake.resident_b, PLONK_ERR_STATE, "run: batch %zu, but %zu witnesses are resident", B, p->intake.resident_b);
+    const plonk_prover::Circuit& c = p->circuit;
+    const plonk_prover::Rounds& r = p->rounds;
+    PLONK_ENTER(c.ctx);
+    plonk_ctx* ctx = c.ctx;
+    const size_t n = c.n, n4 = 4 * n;
+    const unsigned log_n = c.log_n;
     hipStream_t s = ctx->stream;
-    Fq* cxy = p->commit_xy;
-    uint8_t* cfl = p->commit_flags;
+    const Fr* pub = p->intake.pub;
+    ProofState* state = p->results.state;
     PLONK_REQUIRE(B <= 65535, PLONK_ERR_ARG, "batch %zu exceeds 65535 (the proofs are a grid's second dimension)", B);
     PLONK_TRY(ensure_segments(p, B));  // (the options may have changed since the upload)
     const unsigned S = prover_segments(p, B);  // of the three scans (prover_scans.h); 1: one workgroup per proof
 
-    PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 0, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
+    transcript_round(p, B, 0);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
-    PLONK_CHECK_HIP(hipMemsetAsync(p->closes + B, 0, B * sizeof(uint32_t), s));
-    PLONK_LAUNCH(gate_check_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)p->wit_lag, (const Fr*)p->pub, p->n_public,
-                 p->sparse_pi ? (const Fr*)nullptr : (const Fr*)(p->wit_lag + 3 * B * n), (const Fr*)p->fixed_lag, n, B, p->closes + B);  // prover.py:108-116
-    if (p->sparse_pi) {
-        PLONK_TRY(ntt_run(ctx, p->wit_lag, p->coef, log_n, true, 3 * B, n, n, n, nullptr, nullptr, true));
-        if (p->n_public)
-            PLONK_LAUNCH(pi_coeffs_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)p->pub, p->n_public, p->roots_inv, n, B, p->n_inv,
-                         p->coef + 3 * B * n);
-        else
-            PLONK_CHECK_HIP(hipMemsetAsync(p->coef + 3 * B * n, 0, B * n * sizeof(Fr), s));
+    PLONK_CHECK_HIP(hipMemsetAsync(r.closes + B, 0, B * sizeof(uint32_t), s));
+    PLONK_LAUNCH(gate_check_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)r.wit_lag, pub, c.n_public,
+                 c.sparse_pi ? (const Fr*)nullptr : (const Fr*)(r.wit_lag + 3 * B * n), (const Fr*)c.fixed_lag, n, B, r.closes + B);  // prover.py:108-116
+    if (c.sparse_pi) {
+        PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 3 * B, n, n, n, nullptr, nullptr, true));
+        if (c.n_public) PLONK_LAUNCH(pi_coeffs_kernel, grid1(B * n), dim3(256), 0, s, pub, c.n_public, c.roots_inv, n, B, c.n_inv, r.coef + 3 * B * n);
+        else PLONK_CHECK_HIP(hipMemsetAsync(r.coef + 3 * B * n, 0, B * n * sizeof(Fr), s));
     } else {
-        PLONK_TRY(ntt_run(ctx, p->wit_lag, p->coef, log_n, true, 4 * B, n, n, n, nullptr, nullptr, true));
+        PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 4 * B, n, n, n, nullptr, nullptr, true));
     }
-    if (p->lag_srs) PLONK_TRY(msm_run_device(ctx, p->lag_srs, p->wit_lag, n, 3 * B, n, cxy, cfl));  // same points from Lagrange values
-    else PLONK_TRY(msm_run_device(ctx, p->srs, p->coef, n, 3 * B, n, cxy, cfl));
-    PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 1, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
+    PLONK_TRY(commit(p, B, r.wit_lag, r.coef, 3, 0));
+    transcript_round(p, B, 1);
     // ---- round 2: grand product Z, commit                                      prover.py:121-152
     GrandProductIn gp;
     for (int k = 0; k < 3; k++) {
-        gp.abc[k] = p->wit_lag + (size_t)k * B * n;
-        gp.sig[k] = p->fixed_lag + (FX_S1 + k) * n;
+        gp.abc[k] = r.wit_lag + (size_t)k * B * n;
+        gp.sig[k] = c.fixed_lag + (FX_S1 + k) * n;
     }
     // (the three scan families are instrumented for plonk_profile_read: tools/prover_scale.py)
     PLONK_TRY(prof_begin(ctx, "prover_grand_product", 11.0 * 32.0 * (double)n * (double)B));
-    PLONK_TRY(scan_grand_product(s, S, gp, p->roots, p->state, RoundChallenges{}, n, B, p->z_lag, p->closes, p->num, p->wz,
-                                 p->seg));  // num / wz: scratch until round 5
+    PLONK_TRY(scan_grand_product(s, S, gp, c.roots, state, RoundChallenges{}, n, B, r.z_lag, r.closes, r.num, r.wz, r.seg));  // num / wz: scratch until round 5
     PLONK_TRY(prof_end(ctx));
-    PLONK_TRY(ntt_run(ctx, p->z_lag, p->coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
-    if (p->lag_srs) PLONK_TRY(msm_run_device(ctx, p->lag_srs, p->z_lag, n, B, n, cxy + 2 * 3 * B, cfl + 3 * B));
-    else PLONK_TRY(msm_run_device(ctx, p->srs, p->coef + 4 * B * n, n, B, n, cxy + 2 * 3 * B, cfl + 3 * B));
-    PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 2, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
+    PLONK_TRY(ntt_run(ctx, r.z_lag, r.coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(commit(p, B, r.z_lag, r.coef + 4 * B * n, 1, 3));
+    transcript_round(p, B, 2);
     // ---- round 3: coset extensions, fused quotient, back to coefficients, commit T1..T3   prover.py:154-226
     // deg t < 3n: three cosets g mu^r H of the n-th roots of unity determine the quotient, so A, B, C, Z are evaluated on 3n
     // points — per coset a size-n transform of c_i (g mu^r)^i, on the 2^log_n kernel — instead of the reference's 4n, the
     // fused pass runs over 3n points, and three size-n inverse transforms + quotient_combine_kernel give T1, T2, T3
     const size_t n3 = QCOSETS * n;
     const NttFan fan{QCOSETS, 0u, (unsigned)n, (unsigned)n};  // one input, three scalings (g mu^r)^i, outputs [r][n] side by side
-    if (p->sparse_pi) {  // A, B, C and Z through the transform, PI from the Lagrange basis on the coset
-        PLONK_TRY(ntt_run(ctx, p->coef, p->big, log_n, false, 3 * B, n, n, n3, p->g_pow, nullptr, false, &fan));
-        PLONK_TRY(ntt_run(ctx, p->coef + 4 * B * n, p->big + 4 * B * n3, log_n, false, B, n, n, n3, p->g_pow, nullptr, false, &fan));
+    if (c.sparse_pi) {  // A, B, C and Z through the transform, PI from the Lagrange basis on the coset
+        PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 3 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
+        PLONK_TRY(ntt_run(ctx, r.coef + 4 * B * n, r.big + 4 * B * n3, log_n, false, B, n, n, n3, c.g_pow, nullptr, false, &fan));
+        if (c.n_public) PLONK_LAUNCH(pi_coset_kernel, grid1(B * n3), dim3(256), 0, s, pub, c.n_public, (const Fr*)c.li_big, n3, B, r.big + 3 * B * n3);
+        else PLONK_CHECK_HIP(hipMemsetAsync(r.big + 3 * B * n3, 0, B * n3 * sizeof(Fr), s));
     } else {
-        PLONK_TRY(ntt_run(ctx, p->coef, p->big, log_n, false, 5 * B, n, n, n3, p->g_pow, nullptr, false, &fan));
-    }
-    if (p->sparse_pi) {
-        if (p->n_public)
-            PLONK_LAUNCH(pi_coset_kernel, grid1(B * n3), dim3(256), 0, s, (const Fr*)p->pub, p->n_public, (const Fr*)p->li_big, n3, B,
-                         p->big + 3 * B * n3);
-        else
-            PLONK_CHECK_HIP(hipMemsetAsync(p->big + 3 * B * n3, 0, B * n3 * sizeof(Fr), s));
+        PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 5 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
     }
     ZhInv zh;
-    for (int k = 0; k < 4; k++) zh.v[k] = p->zh_inv[k < QCOSETS ? k : 0];
+    for (int k = 0; k < 4; k++) zh.v[k] = c.zh_inv[k < QCOSETS ? k : 0];
     QuotientIn qi;
-    for (int k = 0; k < 5; k++) qi.wit[k] = p->big + (size_t)k * B * n3;
-    for (int k = 0; k < FX_COUNT; k++) qi.fixed[k] = p->fixed_big + (size_t)k * n3;
-    qi.l0 = p->l0_big;
-    qi.xs = p->x_big;
-    PLONK_LAUNCH(quotient_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)B), dim3(256), 0, s, qi, zh, (const ProofState*)p->state, RoundChallenges{},
-                 (unsigned)n3, p->quot, log_n, (unsigned)n4);
+    for (int k = 0; k < 5; k++) qi.wit[k] = r.big + (size_t)k * B * n3;
+    for (int k = 0; k < FX_COUNT; k++) qi.fixed[k] = c.fixed_big + (size_t)k * n3;
+    qi.l0 = c.l0_big;
+    qi.xs = c.x_big;
+    PLONK_LAUNCH(quotient_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)B), dim3(256), 0, s, qi, zh, (const ProofState*)state, RoundChallenges{},
+                 (unsigned)n3, r.quot, log_n, (unsigned)n4);
     const NttFan slices{QCOSETS, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
-    PLONK_TRY(ntt_run(ctx, p->quot, p->quot, log_n, true, B, n, n4, n4, nullptr, p->ginv_pow, false, &slices));
-    PLONK_LAUNCH(quotient_combine_kernel, grid1(B * n), dim3(256), 0, s, p->quot, n, n4, B, p->comb_i, p->comb_g1, p->comb_g2, p->half);
+    PLONK_TRY(ntt_run(ctx, r.quot, r.quot, log_n, true, B, n, n4, n4, nullptr, c.ginv_pow, false, &slices));
+    PLONK_LAUNCH(quotient_combine_kernel, grid1(B * n), dim3(256), 0, s, r.quot, n, n4, B, c.comb_i, c.comb_g1, c.comb_g2, c.half);
     // T1..T3 = the three n-coefficient slices of each quotient row, one batched call (MSM k*B + b = slice k of proof b)
-    PLONK_TRY(msm_run_device(ctx, p->srs, p->quot, n, 3 * B, n4, cxy + 2 * 4 * B, cfl + 4 * B, B, n));
-    PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 3, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
+    PLONK_TRY(msm_run_device(ctx, c.srs, r.quot, n, 3 * B, n4, p->results.commit_xy + 2 * 4 * B, p->results.commit_flags + 4 * B, B, n));
+    transcript_round(p, B, 3);
     // ---- round 4: evaluations                                                  prover.py:228-239
     PLONK_TRY(prof_begin(ctx, "prover_evaluations", 7.0 * 32.0 * (double)n * (double)B));
-    PLONK_TRY(scan_evaluations(s, S, p->coef, p->fixed_coef, p->w, p->state, n, B, p->seg));
+    PLONK_TRY(scan_evaluations(s, S, r.coef, c.fixed_coef, c.w, state, n, B, r.seg));
     PLONK_TRY(prof_end(ctx));
-    PLONK_LAUNCH(transcript_kernel, dim3(tg), dim3(2 * TC_LANES), 0, s, 4, p->state, B, (const Fq*)cxy, (const uint8_t*)cfl, p->chal);
+    transcript_round(p, B, 4);
     // ---- round 5: opening polynomials in coefficient form, commit              prover.py:241-306
-    unsigned gx = (unsigned)((n + 255) / 256);
-    LinWeights* lw = p->lin_w;
-    PLONK_LAUNCH(linearisation_weights_kernel, dim3(tb), dim3(64), 0, s, (const ProofState*)p->state, log_n, p->n_inv, B, lw);
-    PLONK_LAUNCH(linearisation_kernel, dim3(gx, (unsigned)B), dim3(256), 0, s, (const Fr*)p->coef,
-                 (const Fr*)p->fixed_coef, (const Fr*)p->quot, (const LinWeights*)lw, log_n, B, p->num);
+    PLONK_LAUNCH(linearisation_weights_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const ProofState*)state, log_n, c.n_inv, B, r.lin_w);
+    PLONK_LAUNCH(linearisation_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, (const Fr*)r.coef, (const Fr*)c.fixed_coef,
+                 (const Fr*)r.quot, (const LinWeights*)r.lin_w, log_n, B, r.num);
     PLONK_TRY(prof_begin(ctx, "prover_divisions", 2.0 * 3.0 * 32.0 * (double)n * (double)B));
-    const DivideIn dv = {{p->num, p->coef + 4 * B * n}, {p->wz, p->wz + B * n}};  // W_z's numerator by X - zeta, Z by X - zeta w
-    PLONK_TRY(scan_divisions(s, S, dv, p->w, p->state, n, B, p->seg));
+    const DivideIn dv = {{r.num, r.coef + 4 * B * n}, {r.wz, r.wz + B * n}};  // W_z's numerator by X - zeta, Z by X - zeta w
+    PLONK_TRY(scan_divisions(s, S, dv, c.w, state, n, B, r.seg));
     PLONK_TRY(prof_end(ctx));
-    PLONK_TRY(msm_run_device(ctx, p->srs, p->wz, n, 2 * B, n, cxy + 2 * 7 * B, cfl + 7 * B));
+    PLONK_TRY(msm_run_device(ctx, c.srs, r.wz, n, 2 * B, n, p->results.commit_xy + 2 * 7 * B, p->results.commit_flags + 7 * B));
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
 }
@@ -932,9 +639,9 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
 // the condition of the reference's quotient-degree assert, prover.py:205-208).
 static int prover_download(plonk_prover* p, size_t B, uint8_t* out_proofs, uint8_t* out_status, bool compressed) {
     PLONK_REQUIRE(p && B && out_proofs && out_status, PLONK_ERR_ARG, "bad argument");
-    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "download: batch %zu, but %zu witnesses are resident", B, p->resident_b);
-    PLONK_ENTER(p->ctx);
-    plonk_ctx* ctx = p->ctx;
+    PLONK_REQUIRE(B == p->intake.resident_b, PLONK_ERR_STATE, "download: batch %zu, but %zu witnesses are resident", B, p->intake.resident_b);
+    PLONK_ENTER(p->circuit.ctx);
+    plonk_ctx* ctx = p->circuit.ctx;
     void* packed;
     PLONK_TRY(ctx_scratch(ctx, 2, B * (proof_bytes(compressed) + 1), &packed));
     uint8_t *d_proofs = (uint8_t*)packed, *d_status = d_proofs + B * proof_bytes(compressed);
@@ -954,11 +661,11 @@ int plonk_prover_download_compressed(plonk_prover* p, size_t B, uint8_t* out_pro
 
 // Debug / test access: the six challenges of proof b, canonical LE (beta, gamma, alpha, fft_cofactor, zeta, v)
 int plonk_prover_challenges(plonk_prover* p, size_t b, uint8_t out_le32[6 * 32]) {
-    PLONK_REQUIRE(p && b < p->resident_b && out_le32, PLONK_ERR_ARG, "bad argument");
-    PLONK_ENTER(p->ctx);
+    PLONK_REQUIRE(p && b < p->intake.resident_b && out_le32, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(p->circuit.ctx);
     ProofState st;
-    PLONK_CHECK_HIP(hipStreamSynchronize(p->ctx->stream));
-    PLONK_CHECK_HIP(hipMemcpy(&st, p->state + b, sizeof st, hipMemcpyDeviceToHost));
+    PLONK_CHECK_HIP(hipStreamSynchronize(p->circuit.ctx->stream));
+    PLONK_CHECK_HIP(hipMemcpy(&st, p->results.state + b, sizeof st, hipMemcpyDeviceToHost));
     const Fr* ch[6] = {&st.beta, &st.gamma, &st.alpha, &st.fft_cofactor, &st.zeta, &st.v};
     for (int i = 0; i < 6; i++) {
         Fr c = fp_from_mont(*ch[i]);
@@ -1060,20 +767,20 @@ int plonk_fr_quotient(plonk_ctx* ctx, unsigned log_n, const void* const d_evals[
 // and records `done` there, if given: plonk_prover_download, the verifier's load and the send side of plonk_gather_proofs_device.
 int prover_pack_device(plonk_prover* p, size_t B, int compressed, uint8_t* d_proofs, uint8_t* d_status, hipEvent_t done) {
     PLONK_REQUIRE(p && B && d_proofs && d_status, PLONK_ERR_ARG, "bad argument");
-    PLONK_REQUIRE(B == p->resident_b, PLONK_ERR_STATE, "pack: batch %zu, but %zu witnesses are resident", B, p->resident_b);
-    plonk_ctx* ctx = p->ctx;
+    PLONK_REQUIRE(B == p->intake.resident_b, PLONK_ERR_STATE, "pack: batch %zu, but %zu witnesses are resident", B, p->intake.resident_b);
+    plonk_ctx* ctx = p->circuit.ctx;
     const unsigned tb = (unsigned)((B + 63) / 64);
-    PLONK_LAUNCH(pack_proofs_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const Fq*)p->commit_xy, (const ProofState*)p->state, B, d_proofs,
+    PLONK_LAUNCH(pack_proofs_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const Fq*)p->results.commit_xy, (const ProofState*)p->results.state, B, d_proofs,
                  compressed ? 1 : 0);
-    PLONK_LAUNCH(pack_status_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const ProofState*)p->state, (const uint32_t*)p->closes,
-                 (const uint8_t*)p->commit_flags, (const unsigned long long*)p->bad_input, p->bad_stride,
-                 p->solve_valid ? (const uint32_t*)p->solve_bad : (const uint32_t*)nullptr, B, d_status);
+    PLONK_LAUNCH(pack_status_kernel, dim3(tb), dim3(64), 0, ctx->stream, (const ProofState*)p->results.state, (const uint32_t*)p->rounds.closes,
+                 (const uint8_t*)p->results.commit_flags, (const unsigned long long*)p->intake.bad_input, p->intake.bad_stride,
+                 p->solver.valid ? (const uint32_t*)p->solver.bad : (const uint32_t*)nullptr, B, d_status);
     PLONK_CHECK_HIP(hipGetLastError());
     if (done) PLONK_CHECK_HIP(hipEventRecord(done, ctx->stream));
     return PLONK_OK;
 }
 
-plonk_ctx* prover_ctx(plonk_prover* p) { return p->ctx; }
+plonk_ctx* prover_ctx(plonk_prover* p) { return p->circuit.ctx; }
 size_t prover_record_bytes(int compressed) { return proof_bytes(compressed != 0); }
 
 // tests/emu/Makefile compiles verifier.hip as a unit of its own and says so (PLONK_EMU_VERIFIER_UNIT).  A tests/ tree from before

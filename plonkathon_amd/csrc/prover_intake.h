@@ -1,0 +1,279 @@
+// prover_intake.h — how a batch gets into the lock-step prover (internal, included by prover.hip): everything between "bytes from
+// the caller" and "wit_lag, pub, the PI column and resident_b are in place".  The wiring and the solver's plan, the three kinds
+// of upload (wire columns, per-variable values, input values), and what reads the resident variables back.
+//
+// Stream order of an upload.  C = the context's compute stream, H = its copy stream; "sync" and "async" are the two entry points
+// of a kind.  Growing a buffer waits for C first (dev_grow).
+//   wire columns (sync only)   C: memset bad_input (if allocated) · plonk_fr_upload wit_lag [H2D, checked conversion, wait]
+//                                 · plonk_fr_upload pub [the same] · PI column · wait
+//   variables, sync            C: memset bad_input · plonk_fr_upload vars [H2D, checked conversion, wait] · GATHER · wait
+//   variables, async           H: wait vars.read (if pending) · H2D vars · record ev_copied
+//                              C: wait ev_copied · checked conversion in place [memset bad_input, kernel] · GATHER
+//   inputs, sync               C: H2D inputs · SOLVE · GATHER · D2H bad_input · wait
+//   inputs, async              H: wait inputs.read (if pending) · H2D inputs · record ev_copied
+//                              C: wait ev_copied · SOLVE · GATHER
+//   SOLVE  = memset bad_input · witness_seed_kernel · record inputs.read · [prof] witness_solve_kernel [prof]
+//   GATHER = witness_scatter_kernel · public_gather_kernel (if n_public) · PI column · record vars.read
+//   PI column = memset (n_public == 0) | pi_fill_kernel (dense PI) | nothing (sparse PI: round 1 builds it from pub)
+// The solver writes `vars` in place: on C it is behind the previous batch's gathers, the only readers, so only the staging buffer
+// that H writes needs its `read` event.  An async path's canonical-range verdict comes back as PROVER_ST_BAD_INPUT of the download.
+#pragma once
+#include <string.h>
+
+#include "witness_solve.h"  // prover.h; the plan, the solver's kernels
+
+static int ensure_batch(plonk_prover* p, size_t B);  // prover.hip: the per-batch buffers of B proofs
+
+// witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
+__global__ void pi_fill_kernel(const Fr* pub, size_t n_public, size_t n, size_t B, Fr* pi) {
+    const size_t total = B * n;
+    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = gI / n, i = gI - b * n;
+        Fr v = fp_zero<FrParams>();
+        if (i < n_public) v = fp_neg(fp_load(pub + b * n_public + i));
+        fp_store(pi + gI, v);
+    }
+}
+
+// prover.py:94-103 on the device: A[i], B[i], C[i] = witness[wires[i].L / R / O], witness[None] = 0, zero padded to n.
+// vars = [B][V] variable values; cell[3][n] = variable index of each wire cell (V: empty); out = wit_lag [3][B][n].
+__global__ void witness_scatter_kernel(const Fr* vars, const uint32_t* cell, size_t V, size_t n, size_t B, Fr* out) {
+    const size_t total = 3 * B * n;
+    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = gI / (B * n), r = gI - j * B * n, b = r / n, i = r - b * n;
+        const uint32_t idx = cell[j * n + i];
+        fp_store(out + gI, idx < V ? fp_load(vars + b * V + idx) : fp_zero<FrParams>());
+    }
+}
+__global__ void public_gather_kernel(const Fr* vars, const uint32_t* pub_index, size_t V, size_t l, size_t B, Fr* pub) {
+    const size_t total = B * l;
+    for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = gI / l, k = gI - b * l;
+        fp_store(pub + gI, fp_load(vars + b * V + pub_index[k]));
+    }
+}
+
+// the wiring's, the solver's and the staging's share of plonk_prover_create and plonk_prover_destroy
+static int intake_init(plonk_prover* p, const uint8_t* selectors_le32) {
+    p->solver.gates_host = (uint8_t*)malloc(5 * p->circuit.n * 32);  // QM .. QC as given: what plonk_prover_set_inputs classifies
+    PLONK_REQUIRE(p->solver.gates_host, PLONK_ERR_NOMEM, "out of host memory");
+    memcpy(p->solver.gates_host, selectors_le32, 5 * p->circuit.n * 32);
+    return PLONK_OK;
+}
+static void intake_destroy(plonk_prover* p) {
+    dev_free_all({(void**)&p->intake.vars.buf, (void**)&p->intake.inputs.buf, (void**)&p->intake.bad_input, (void**)&p->wiring.cell_index,
+                  (void**)&p->wiring.pub_index, (void**)&p->solver.desc, (void**)&p->solver.input_index, (void**)&p->solver.bad});
+    for (hipEvent_t ev : {p->intake.vars.read, p->intake.inputs.read, p->intake.ev_copied})  // each exists only if an upload created it
+        if (ev) hipEventDestroy(ev);
+    free(p->solver.gates_host);
+    free(p->wiring.cell_host);
+}
+
+// The caller's bytes into a staging buffer.  async: on the copy stream, behind the previous batch's last read of the buffer; the
+// compute stream goes on behind the copy.  Otherwise on the compute stream.
+static int staging_copy(plonk_prover* p, Staging* st, const uint8_t* src, size_t bytes, bool async) {
+    plonk_ctx* ctx = p->circuit.ctx;
+    if (!async) {
+        PLONK_CHECK_HIP(hipMemcpyAsync(st->buf, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return PLONK_OK;
+    }
+    PLONK_TRY(ctx_copy_stream(ctx));
+    if (st->read_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->copy_stream, st->read, 0));
+    PLONK_CHECK_HIP(hipMemcpyAsync(st->buf, src, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    PLONK_CHECK_HIP(hipEventRecord(p->intake.ev_copied, ctx->copy_stream));
+    PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, p->intake.ev_copied, 0));
+    return PLONK_OK;
+}
+
+// the PI column of the B uploaded witnesses, wit_lag[3]: -public inputs, then zeros (the sparse form is built from `pub` in round 1)
+static int fill_pi_column(plonk_prover* p, size_t B) {
+    const size_t n = p->circuit.n, l = p->circuit.n_public;
+    hipStream_t s = p->circuit.ctx->stream;
+    Fr* pi = p->rounds.wit_lag + 3 * B * n;
+    if (!l) PLONK_CHECK_HIP(hipMemsetAsync(pi, 0, B * n * sizeof(Fr), s));
+    else if (!p->circuit.sparse_pi) PLONK_LAUNCH(pi_fill_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)p->intake.pub, l, n, B, pi);
+    PLONK_CHECK_HIP(hipGetLastError());
+    return PLONK_OK;
+}
+
+// Per-variable values of a batch, uploaded ([B][n_vars] canonical LE, n_vars * 32 bytes per proof instead of 3 * n * 32) or, from_inputs,
+// solved from [B][n_inputs] input values; the wire columns and the public inputs are gathered from them on the device (prover.py:94-103,
+// 57-62).  async (order: the head of this file): nothing waits on the host, the copy overlaps whatever the compute stream is running; the
+// caller keeps src_le32 alive, in pinned memory (plonk_host_alloc) for a copy that really is asynchronous, until the batch is downloaded.
+static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, bool from_inputs, bool async) {
+    // begin: the checks, every buffer and event the batch needs, and no batch resident (a failed upload leaves none to run)
+    PLONK_REQUIRE(p && src_le32 && B, PLONK_ERR_ARG, "bad argument");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    PLONK_REQUIRE(p->wiring.n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    PLONK_REQUIRE(p->solver.n_inputs || !from_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
+    PLONK_TRY(ensure_batch(p, B));
+    plonk_prover::Intake& in = p->intake;
+    hipStream_t s = ctx->stream;
+    const size_t n = p->circuit.n, l = p->circuit.n_public, V = p->wiring.n_vars, K = p->solver.n_inputs;
+    PLONK_TRY(dev_grow(s, &in.vars.cap, B * V, {{(void**)&in.vars.buf, B * V * sizeof(Fr)}}));
+    if (from_inputs) PLONK_TRY(dev_grow(s, &in.inputs.cap, B, {{(void**)&in.inputs.buf, B * K * sizeof(Fr)}, {(void**)&p->solver.bad, B * sizeof(uint32_t)}}));
+    if (!in.bad_input) PLONK_TRY(dev_alloc((void**)&in.bad_input, sizeof(unsigned long long)));
+    if (!in.ev_copied) PLONK_CHECK_HIP(hipEventCreate(&in.ev_copied));
+    if (!in.vars.read) PLONK_CHECK_HIP(hipEventCreate(&in.vars.read));
+    if (from_inputs && !in.inputs.read) PLONK_CHECK_HIP(hipEventCreate(&in.inputs.read));
+    in.resident_b = 0;
+    in.vars_valid = p->solver.valid = false;
+    in.bad_stride = from_inputs ? K : V;
+    // convert: `vars` of the batch in Montgomery form, and the verdict on the uploaded values in *bad_input
+    if (from_inputs) {
+        PLONK_TRY(staging_copy(p, &in.inputs, src_le32, B * K * sizeof(Fr), async));
+        PLONK_CHECK_HIP(hipMemsetAsync(in.bad_input, 0xff, sizeof(unsigned long long), s));
+        PLONK_LAUNCH(witness_seed_kernel, grid1(B * K), dim3(256), 0, s, (const Fr*)in.inputs.buf, (const uint32_t*)p->solver.input_index, K, V, B,
+                     in.vars.buf, in.bad_input, p->solver.bad);
+        PLONK_CHECK_HIP(hipEventRecord(in.inputs.read, s));
+        in.inputs.read_pending = true;
+        PLONK_TRY(prof_begin(ctx, "witness_solve", 32.0 * (double)V * (double)B));
+        PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
+                     (const uint32_t*)p->wiring.cell_index, (const Fr*)p->circuit.fixed_lag, V, n, p->solver.rows, B, p->solver.bad);
+        PLONK_TRY(prof_end(ctx));
+    } else if (async) {
+        PLONK_TRY(staging_copy(p, &in.vars, src_le32, B * V * sizeof(Fr), true));
+        PLONK_TRY(k_fr_to_mont_checked(ctx, in.vars.buf, B * V, in.bad_input));
+    } else {
+        PLONK_CHECK_HIP(hipMemsetAsync(in.bad_input, 0xff, sizeof(unsigned long long), s));
+        PLONK_TRY(plonk_fr_upload(ctx, in.vars.buf, src_le32, B * V));  // waits, and reports a non-canonical value as PLONK_ERR_ARG
+    }
+    // finish: the wire columns, the public inputs and the PI column from `vars` (vars.read marks its last read); sync: the host waits,
+    // and inputs that were only enqueued for their check get their verdict read back
+    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, s, (const Fr*)in.vars.buf, (const uint32_t*)p->wiring.cell_index, V, n, B,
+                 p->rounds.wit_lag);
+    if (l) PLONK_LAUNCH(public_gather_kernel, grid1(B * l), dim3(256), 0, s, (const Fr*)in.vars.buf, (const uint32_t*)p->wiring.pub_index, V, l, B, in.pub);
+    PLONK_TRY(fill_pi_column(p, B));
+    PLONK_CHECK_HIP(hipEventRecord(in.vars.read, s));
+    in.vars.read_pending = true;
+    unsigned long long first_bad = ~0ull;
+    if (!async && from_inputs) PLONK_CHECK_HIP(hipMemcpyAsync(&first_bad, in.bad_input, sizeof first_bad, hipMemcpyDeviceToHost, s));
+    if (!async) PLONK_CHECK_HIP(hipStreamSynchronize(s));
+    PLONK_REQUIRE(first_bad == ~0ull, PLONK_ERR_ARG, "input %llu of proof %llu is not a canonical Fr value (>= r)", first_bad % K, first_bad / K);
+    in.resident_b = B;
+    in.vars_valid = true;
+    p->solver.valid = from_inputs;
+    return PLONK_OK;
+}
+
+extern "C" {
+
+// witness columns [3][B][n] (A, B, C) and public inputs [B][n_public], canonical LE
+int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t B) {
+    PLONK_REQUIRE(p && abc_le32 && B && (public_le32 || !p->circuit.n_public), PLONK_ERR_ARG, "bad argument");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    PLONK_TRY(ensure_batch(p, B));
+    if (p->intake.bad_input) PLONK_CHECK_HIP(hipMemsetAsync(p->intake.bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
+    PLONK_TRY(plonk_fr_upload(ctx, p->rounds.wit_lag, abc_le32, 3 * B * p->circuit.n));
+    if (p->circuit.n_public) PLONK_TRY(plonk_fr_upload(ctx, p->intake.pub, public_le32, B * p->circuit.n_public));
+    PLONK_TRY(fill_pi_column(p, B));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    p->intake.resident_b = B;
+    p->intake.vars_valid = p->solver.valid = false;
+    return PLONK_OK;
+}
+
+// cell_index[3][n]: variable index carried by each wire cell (column L/R/O, row), n_vars for an empty cell or a
+// padding row; public_index[n_public]: the public variables, in the order of the public rows (prover.py:57-62).
+int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars) {
+    PLONK_REQUIRE(p && cell_index && n_vars && (public_index || !p->circuit.n_public), PLONK_ERR_ARG, "bad argument");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    plonk_prover::Wiring& w = p->wiring;
+    const size_t cells = 3 * p->circuit.n, l = p->circuit.n_public;
+    for (size_t k = 0; k < cells; k++)
+        PLONK_REQUIRE(cell_index[k] <= n_vars, PLONK_ERR_ARG, "wire cell %zu names variable %u of %zu", k, cell_index[k], n_vars);
+    for (size_t k = 0; k < l; k++)
+        PLONK_REQUIRE(public_index[k] < n_vars, PLONK_ERR_ARG, "public input %zu names variable %u of %zu", k, public_index[k], n_vars);
+    if (!w.cell_index) PLONK_TRY(dev_alloc((void**)&w.cell_index, cells * sizeof(uint32_t)));
+    if (!w.pub_index) PLONK_TRY(dev_alloc((void**)&w.pub_index, (l + 1) * sizeof(uint32_t)));
+    PLONK_CHECK_HIP(hipMemcpyAsync(w.cell_index, cell_index, cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (l) PLONK_CHECK_HIP(hipMemcpyAsync(w.pub_index, public_index, l * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!w.cell_host) w.cell_host = (uint32_t*)malloc(cells * sizeof(uint32_t));
+    PLONK_REQUIRE(w.cell_host, PLONK_ERR_NOMEM, "out of host memory");
+    memcpy(w.cell_host, cell_index, cells * sizeof(uint32_t));
+    w.n_vars = n_vars;
+    p->solver.n_inputs = 0;  // a plan belongs to the wiring it was built from
+    p->intake.vars_valid = false;
+    return PLONK_OK;
+}
+
+int plonk_prover_upload_variables(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload(p, vars_le32, B, false, false); }
+int plonk_prover_upload_variables_async(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload(p, vars_le32, B, false, true); }
+
+// The circuit's inputs: the variables a batch will give values for.  Builds the solver's plan from the gate columns
+// plonk_prover_create was given and the wiring; a refusal that names a variable (one that no row assigns before it is read, or
+// at all) sets *out_missing_var to it, any other sets it to 0xffffffff.
+int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t n_inputs, uint32_t* out_missing_var) {
+    PLONK_REQUIRE(p && input_index && n_inputs && out_missing_var, PLONK_ERR_ARG, "bad argument");
+    *out_missing_var = SOLVE_NO_VARIABLE;
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    PLONK_REQUIRE(p->wiring.n_vars && p->wiring.cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    plonk_prover::Solver& sv = p->solver;
+    std::vector<uint32_t> desc;
+    PLONK_TRY(solve_plan_build(sv.gates_host, p->wiring.cell_host, p->circuit.n, p->wiring.n_vars, input_index, n_inputs, desc, out_missing_var));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // a batch in flight still walks the old plan
+    sv.n_inputs = 0;
+    p->intake.resident_b = 0;
+    dev_free_all({(void**)&sv.desc, (void**)&sv.input_index, (void**)&p->intake.inputs.buf, (void**)&sv.bad});
+    p->intake.inputs.cap = 0;
+    PLONK_TRY(dev_alloc((void**)&sv.desc, desc.size() * sizeof(uint32_t)));
+    PLONK_TRY(dev_alloc((void**)&sv.input_index, n_inputs * sizeof(uint32_t)));
+    if (!desc.empty()) PLONK_CHECK_HIP(hipMemcpyAsync(sv.desc, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipMemcpyAsync(sv.input_index, input_index, n_inputs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    sv.rows = (uint32_t)desc.size();
+    sv.n_inputs = n_inputs;
+    return PLONK_OK;
+}
+
+int plonk_prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload(p, inputs_le32, B, true, false); }
+int plonk_prover_upload_inputs_async(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_upload(p, inputs_le32, B, true, true); }
+
+// [B][k] canonical LE values of the variables var_index[0 .. k) of the resident batch (var_index == NULL: all n_vars, k
+// ignored), after either kind of variable upload: what the solver computed — a public input among it — for the verifier
+int plonk_prover_download_variables(plonk_prover* p, size_t B, const uint32_t* var_index, size_t k, uint8_t* out_le32) {
+    PLONK_REQUIRE(p && B && out_le32 && (k || !var_index), PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(B == p->intake.resident_b, PLONK_ERR_STATE, "download_variables: batch %zu, but %zu witnesses are resident", B, p->intake.resident_b);
+    PLONK_REQUIRE(p->intake.vars_valid, PLONK_ERR_STATE, "the resident batch was uploaded as wire columns: it has no variable values");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    const size_t V = p->wiring.n_vars;
+    if (!var_index) k = V;
+    for (size_t j = 0; var_index && j < k; j++)
+        PLONK_REQUIRE(var_index[j] < V, PLONK_ERR_ARG, "index %zu names variable %u of %zu", j, var_index[j], V);
+    void* tmp;
+    PLONK_TRY(ctx_scratch(ctx, 3, B * k * sizeof(Fr) + k * sizeof(uint32_t), &tmp));
+    Fr* vals = (Fr*)tmp;
+    uint32_t* d_index = nullptr;
+    if (var_index) {
+        d_index = reinterpret_cast<uint32_t*>(vals + B * k);
+        PLONK_CHECK_HIP(hipMemcpyAsync(d_index, var_index, k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    PLONK_LAUNCH(variable_gather_kernel, grid1(B * k), dim3(256), 0, ctx->stream, (const Fr*)p->intake.vars.buf, (const uint32_t*)d_index, V, k, B, vals);
+    PLONK_CHECK_HIP(hipGetLastError());
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_le32, vals, B * k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return PLONK_OK;
+}
+
+// per proof of the resident batch, 0 or 1 + the first row whose check failed (PROVER_ST_ASSERT); a batch that did not come
+// through the solver has none
+int plonk_prover_solve_failures(plonk_prover* p, size_t B, uint32_t* out_rows) {
+    PLONK_REQUIRE(p && B && out_rows, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(B == p->intake.resident_b, PLONK_ERR_STATE, "solve_failures: batch %zu, but %zu witnesses are resident", B, p->intake.resident_b);
+    PLONK_ENTER(p->circuit.ctx);
+    if (!p->solver.valid) {
+        memset(out_rows, 0, B * sizeof(uint32_t));
+        return PLONK_OK;
+    }
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_rows, p->solver.bad, B * sizeof(uint32_t), hipMemcpyDeviceToHost, p->circuit.ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(p->circuit.ctx->stream));
+    return PLONK_OK;
+}
+
+}  // extern "C"

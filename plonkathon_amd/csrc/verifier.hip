@@ -487,10 +487,10 @@ int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs, const uint8_t*
 
 int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch, const uint8_t seed[32]) {
     PLONK_REQUIRE(v && p && batch && seed, PLONK_ERR_ARG, "bad argument");
-    PLONK_REQUIRE(p->ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->ctx->device, v->ctx->device);
-    PLONK_REQUIRE(p->log_n == v->log_n && p->n_public == v->n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %zu)",
-                  p->log_n, p->n_public, v->log_n, v->n_public);
-    PLONK_REQUIRE(batch == p->resident_b, PLONK_ERR_STATE, "verify: batch %zu, but %zu proofs are resident in the prover", batch, p->resident_b);
+    PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->circuit.ctx->device, v->ctx->device);
+    PLONK_REQUIRE(p->circuit.log_n == v->log_n && p->circuit.n_public == v->n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %zu)",
+                  p->circuit.log_n, p->circuit.n_public, v->log_n, v->n_public);
+    PLONK_REQUIRE(batch == p->intake.resident_b, PLONK_ERR_STATE, "verify: batch %zu, but %zu proofs are resident in the prover", batch, p->intake.resident_b);
     PLONK_ENTER(v->ctx);
     v->batch = 0;
     PLONK_TRY(verifier_ensure(v, batch));
@@ -499,7 +499,7 @@ int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch,
     PLONK_TRY(prover_pack_device(p, batch, 0, v->d_proofs, v->d_status, v->ev));
     PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->ev, 0));
     if (v->n_public)
-        PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->pub, batch * v->n_public * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
+        PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->intake.pub, batch * v->n_public * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
     return verifier_run(v, batch, seed);
 }
 

@@ -28,3 +28,18 @@ ubsan:
 	$(CXX) $(CXXFLAGS) -O1 -g $(UBSAN) -c comm_stub.cpp -o ubsan/comm_stub.o
 	$(CXX) -shared $(UBSAN) -o ubsan/libplonk_emu.so ubsan/*.o
 
+# A stand-alone program under AddressSanitizer AND UBSan, with its own main (nothing is loaded into Python, no LD_PRELOAD): the
+# prover's intake (csrc/prover_intake.h) — buffers and events across batches of 2, 5 and 1 through every kind of upload, a second
+# plan, a prover destroyed without an upload.      make -C tests/emu -j8 intake-sanitize
+SAN_BOTH := -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
+asan/intake/%.o: $(CSRC)/%.hip $(HDRS)
+	@mkdir -p asan/intake
+	$(CXX) $(CXXFLAGS) $(SAN_BOTH) -x c++ -c $< -o $@
+asan/intake/%.o: %.cpp $(HDRS)
+	@mkdir -p asan/intake
+	$(CXX) $(CXXFLAGS) $(SAN_BOTH) -I../../include -c $< -o $@
+asan/intake_lifetime: $(SRCS:$(CSRC)/%.hip=asan/intake/%.o) asan/intake/hip_emu.o asan/intake/comm_stub.o asan/intake/intake_lifetime.o
+	$(CXX) $(SAN_BOTH) -o $@ $^
+intake-sanitize: asan/intake_lifetime
+	ASAN_OPTIONS=detect_stack_use_after_return=0 ./asan/intake_lifetime
+.PHONY: intake-sanitize

@@ -61,3 +61,23 @@ def test_non_canonical_inputs(emu, setup):
 
 def test_existing_uploads_unchanged(emu, setup):
     wc.existing_uploads_unchanged(setup)
+
+
+def test_batch_sizes_change_between_uploads(emu, setup):
+    wc.batch_sizes_change_between_uploads(setup)
+
+
+def test_intake_lifetime_program(emu_cdll, tmp_path):
+    """tests/emu/intake_lifetime.cpp — the stand-alone program of `make -C tests/emu intake-sanitize` — built plain against the
+    emulator library and run: batches of 2, 5 and 1 through every kind of upload, two plans, a prover destroyed without an upload.
+    The emulator's events are heap objects, so an event destroyed twice or never created ends the program."""
+    import os
+    import subprocess
+
+    emu_dir = os.path.dirname(os.path.abspath(emu_cdll._name))
+    repo = os.path.dirname(os.path.dirname(emu_dir))
+    exe = str(tmp_path / "intake_lifetime")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(repo, "include"), os.path.join(emu_dir, "intake_lifetime.cpp"), "-o", exe,
+                    emu_cdll._name, "-Wl,-rpath," + emu_dir], check=True, timeout=120)
+    done = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert done.returncode == 0 and done.stdout.strip() == "intake_lifetime ok", (done.returncode, done.stdout, done.stderr)

@@ -78,3 +78,7 @@ def test_two_async_batches_back_to_back(setup):
 
 def test_public_values_feed_the_verifier(setup, shared):
     wc.public_values_feed_the_verifier(setup, shared)
+
+
+def test_batch_sizes_change_between_uploads(setup):
+    wc.batch_sizes_change_between_uploads(setup)

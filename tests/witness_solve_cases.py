@@ -298,6 +298,65 @@ def existing_uploads_unchanged(setup):
     assert bp.ctx.L.plonk_prover_download_variables(bp._h, 1, None, 0, ctypes.create_string_buffer(32 * 5)) == ERR_STATE
 
 
+# ---- 8. batch sizes and upload kinds change on one prover -------------------------------------------------------------------
+def batch_sizes_change_between_uploads(setup, n=32):
+    """One prover of the chain circuit: B = 2 from inputs, B = 5 from packed variable values, B = 1 from wire columns, B = 5 from
+    inputs asynchronously out of a page-locked buffer.  Every buffer grows once (`vars`, `inputs`, the segments' scratch, the batch),
+    a smaller batch then reuses the larger buffers, and the two staging buffers hand over to each other.  After each upload the
+    proof and status bytes are those of a fresh prover given the same batch."""
+    lines = chain_lines(n)
+    program = pa.Program(lines, n)
+    starts = [[{"x0": 3 + 11 * b} for b in range(2)], [{"x0": 500 + 7 * b} for b in range(5)], [{"x0": 90001}],
+              [{"x0": 77 + 1000003 * b} for b in range(5)]]
+    wits = [oracle_fill(lines, n, s) for s in starts]
+    le = lambda vals: b"".join(int(v % R_MOD).to_bytes(32, "little") for v in vals)
+
+    def proved(bp, B):
+        bp.run()
+        raw, st = bp.download_raw()
+        assert st == bytes(B) and len(raw) == 768 * B
+        return raw, st
+
+    def fresh(upload):
+        ref = pa.BatchProver(setup, program)
+        B = upload(ref)
+        return proved(ref, B)
+
+    def from_inputs(s):
+        return lambda q: (q.upload_inputs([dict(d) for d in s]), len(s))[1]
+
+    def from_values(w):
+        return lambda q: (q.upload_values(le([x[v] for x in w for v in q.variables]), len(w)), len(w))[1]
+
+    def from_columns(w):
+        return lambda q: (q._upload_columns([dict(x) for x in w]), len(w))[1]
+
+    bp = pa.BatchProver(setup, program)
+    seen = []
+    for step, upload in enumerate([from_inputs(starts[0]), from_values(wits[1]), from_columns(wits[2])]):
+        B = upload(bp)
+        got = proved(bp, B)
+        assert got == fresh(upload), step
+        seen.append(got[0])
+        if step == 2:  # wire columns: no solver verdicts, no variable values
+            assert bp.solve_failures() == [None]
+            assert bp.ctx.L.plonk_prover_download_variables(bp._h, 1, None, 0, ctypes.create_string_buffer(32 * len(bp.variables))) == ERR_STATE
+        else:
+            assert_variables(bp, wits[step], ("sizes", step))
+    assert bp.inputs == ("x0",)
+    blob = le([d["x0"] for d in starts[3]])
+    pinned = bp.ctx.host_alloc(len(blob))
+    pinned[: len(blob)] = blob
+    bp.upload_input_values_async(pinned, 5)
+    got = proved(bp, 5)
+    assert got == fresh(from_inputs(starts[3]))
+    assert_variables(bp, wits[3], ("sizes", 3))
+    assert bp.solve_failures() == [None] * 5
+    bp.ctx.host_free(pinned)
+    seen.append(got[0])
+    assert len(set(seen)) == 4 and seen[1] != seen[3]  # four different batches
+
+
 # ---- GPU only ----------------------------------------------------------------------------------------------------------------
 def lane_geometry(setup, B, n=32):
     """One lane per proof in 64-lane workgroups: B proofs with distinct x0, every variable of every proof."""
