@@ -251,9 +251,17 @@ int plonk_prover_destroy(plonk_prover* p);
  * round 5's two divisions) run cut into S = 2^k segments per proof, each as two or three launches over (S, batch) workgroups,
  * instead of one workgroup per proof; k = 0 forces the one-workgroup kernels.  Bits 8-11 hold k + 1; zero there = automatic
  * (plonk_prover_plan_segments: S > 1 only where `batch` workgroups leave the chip idle and the circuit is large).  Same proofs,
- * bit for bit.  PLONK_ERR_ARG for S > 256, for segments of fewer than 16 rows, and for any bit outside the two options. */
+ * bit for bit.  PLONK_ERR_ARG for S > 256, for segments of fewer than 16 rows, and for any bit outside the options. */
 #define PLONK_PROVER_SEGMENTS_LOG2(k) ((((unsigned)(k) + 1u) & 15u) << 8)
 #define PLONK_PROVER_SEGMENTS_MASK (15u << 8)
+/* PLONK_PROVER_SOLVE_FORM(k), tests and A/B runs: which kernel plonk_prover_upload_inputs* solves a batch with, from the next such
+ * upload on.  Bits 16-17 hold k: 0 = automatic (plonk_prover_solve_plan reports the choice), PLONK_PROVER_SOLVE_LANES = one lane per
+ * proof walks the rows in program order, PLONK_PROVER_SOLVE_LEVELS = one workgroup per proof, its lanes take the rows of one
+ * dependency level at a time.  Same variables, same verdicts, bit for bit.  k = 3 is PLONK_ERR_ARG. */
+#define PLONK_PROVER_SOLVE_FORM(k) (((unsigned)(k) & 3u) << 16)
+#define PLONK_PROVER_SOLVE_FORM_MASK (3u << 16)
+#define PLONK_PROVER_SOLVE_LANES 1u
+#define PLONK_PROVER_SOLVE_LEVELS 2u
 int plonk_prover_set_options(plonk_prover* p, unsigned flags);
 int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t batch);
 /* The same inputs at n_vars * 32 bytes per proof instead of 3 * n * 32: the wiring is given once per circuit —
@@ -454,6 +462,11 @@ int plonk_msm_configure(plonk_ctx* ctx, unsigned window_bits, unsigned groups);
 /* the number of segments the lock-step prover (and plonk_fr_grand_product, batch = 1) cuts the per-proof scans of `batch` proofs
  * of 2^log_n rows into on ctx's device when PLONK_PROVER_SEGMENTS_LOG2 is not set: 1 = one workgroup per proof */
 int plonk_prover_plan_segments(plonk_ctx* ctx, unsigned log_n, size_t batch, unsigned* out_segments);
+/* the witness solver's plan (plonk_prover_set_inputs) and the form the automatic rule solves `batch` proofs in: out = rows walked
+ * (up to the last row that is not skipped), active rows, dependency levels, rows of the widest level, T = lanes of the levelised
+ * kernel's workgroup (64 where no level is wider), the rule's pick for `batch` (PLONK_PROVER_SOLVE_LANES / _LEVELS), and the
+ * levelised form's steps = the sum over the levels of ceil(width / T).  PLONK_ERR_STATE without a plan. */
+int plonk_prover_solve_plan(plonk_prover* p, size_t batch, uint32_t out[7]);
 
 /* ---- timing support for bench.py (HIP events on the context's stream) ------------------------ */
 int plonk_timer_start(plonk_ctx* ctx);

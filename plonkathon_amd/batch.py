@@ -36,13 +36,19 @@ except ImportError:  # pragma: no cover - pure-Python equivalent of the packer (
 
 
 class BatchProver:
-    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False, segments=None):
+    SOLVE_FORMS = {None: 0, "lanes": 1, "levels": 2}  # PLONK_PROVER_SOLVE_FORM
+
+    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False, segments=None, solve=None):
         """`ctx`: the Context (HIP stream) to run on; several BatchProvers on distinct contexts of one
         GPU overlap each other's latency-bound kernels (transcript, inversions) with MSM work.
         `lagrange_commits`: commit a_1, b_1, c_1, z_1 from Lagrange values over the Lagrange-basis SRS
         (PLONK_PROVER_LAGRANGE_COMMITS) instead of from coefficient forms; same proofs.
         `segments`: None = automatic (`segments_for`); a power of two S forces the per-proof scans of rounds 2, 4 and 5 to run
-        cut into S segments per proof (PLONK_PROVER_SEGMENTS_LOG2; 1 = one workgroup per proof): tests and A/B runs, same proofs."""
+        cut into S segments per proof (PLONK_PROVER_SEGMENTS_LOG2; 1 = one workgroup per proof): tests and A/B runs, same proofs.
+        `solve`: None = automatic (`solve_plan`); "lanes" / "levels" force the witness solver of `upload_inputs*` to run one lane
+        per proof / one workgroup per proof over dependency levels (PLONK_PROVER_SOLVE_FORM): tests and A/B runs, same values."""
+        if solve not in self.SOLVE_FORMS:
+            raise ValueError('solve must be None, "lanes" or "levels"')
         self.group_order = program.group_order
         self.setup = setup
         self.program = program
@@ -67,6 +73,7 @@ class BatchProver:
             if segments < 1 or segments & (segments - 1):
                 raise ValueError("segments must be a power of two")
             flags |= min(segments.bit_length(), 15) << 8  # k + 1 in bits 8-11; the library checks the range
+        flags |= self.SOLVE_FORMS[solve] << 16
         if flags:
             check(self.ctx.L.plonk_prover_set_options(self._h, flags))
         # the wiring goes to the device once; a batch is then only the variables' values (V x 32 B per proof)
@@ -94,6 +101,15 @@ class BatchProver:
         out = ctypes.c_uint(0)
         check(self.ctx.L.plonk_prover_plan_segments(self.ctx.handle, _log2_exact(self.group_order), B, ctypes.byref(out)))
         return out.value
+
+    def solve_plan(self, B):
+        """The witness solver's plan (after `set_inputs`) and the form a batch of B is solved in when `solve` was not given:
+        rows walked, active rows, dependency levels, the widest level, the levelised kernel's workgroup size, its steps."""
+        out = (ctypes.c_uint32 * 7)()
+        check(self.ctx.L.plonk_prover_solve_plan(self._h, B, out))
+        rows, active, levels, widest, threads, form, steps = out
+        return {"rows": rows, "active_rows": active, "levels": levels, "widest": widest, "threads": threads, "steps": steps,
+                "form": {1: "lanes", 2: "levels"}[form]}
 
     # ---- inputs ---------------------------------------------------------------------------------
     def wire_columns(self, witness):

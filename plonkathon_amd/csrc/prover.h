@@ -82,6 +82,7 @@ struct plonk_prover {
     } circuit;
     plonk_srs* lag_srs;   // plonk_prover_set_options: Lagrange-basis view of srs (PLONK_PROVER_LAGRANGE_COMMITS), owned by srs
     unsigned seg_forced;  // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
+    unsigned solve_forced;  // PLONK_PROVER_SOLVE_FORM: PLONK_PROVER_SOLVE_LANES or PLONK_PROVER_SOLVE_LEVELS for every input upload, 0 = solve_plan_form
     // ---- what the five rounds read and write: per-batch buffers (capacity cap_b proofs; prover.hip: batch_buffers)
     struct Rounds {
         size_t cap_b;
@@ -121,6 +122,10 @@ struct plonk_prover {
         uint8_t* gates_host;       // [5][n] canonical LE: QM, QL, QR, QO, QC as plonk_prover_create was given them
         uint32_t* desc;            // [rows] one descriptor per row (device)
         uint32_t rows;             // rows the solver walks: up to the last one that is not skipped
+        // the levelised form's schedule (SolvePlan): built, freed and dropped with desc
+        uint32_t* order;           // [active] the rows that are not skipped, sorted by level (device)
+        uint32_t* level_start;     // [levels + 1] (device)
+        uint32_t active, levels, widest, threads, steps;
         uint32_t* input_index;     // [n_inputs] the input variables (device)
         size_t n_inputs;           // 0: no plan (plonk_prover_set_inputs has not been called since the wiring was set)
         uint32_t* bad;             // [B] 0, or 1 + the first row whose check failed (capacity: intake.inputs.cap proofs)

@@ -517,12 +517,16 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
 extern "C" {
 
 int plonk_prover_set_options(plonk_prover* p, unsigned flags) {
-    PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK)), PLONK_ERR_ARG, "unknown prover option bits %#x", flags);
+    PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK | PLONK_PROVER_SOLVE_FORM_MASK)), PLONK_ERR_ARG,
+                  "unknown prover option bits %#x", flags);
     PLONK_ENTER(p->circuit.ctx);
     const unsigned seg = (flags & PLONK_PROVER_SEGMENTS_MASK) >> 8;  // k + 1, 0 = automatic
     PLONK_REQUIRE(seg <= 9 && (!seg || (p->circuit.n >> (seg - 1)) >= 16), PLONK_ERR_ARG,
                   "2^%u segments: at most 256, of at least 16 rows each (group_order %zu)", seg ? seg - 1 : 0, p->circuit.n);
+    const unsigned form = (flags & PLONK_PROVER_SOLVE_FORM_MASK) >> 16;  // 0 = automatic
+    PLONK_REQUIRE(form <= PLONK_PROVER_SOLVE_LEVELS, PLONK_ERR_ARG, "solve form %u: 0 (automatic), 1 (one lane per proof) or 2 (levels)", form);
     p->seg_forced = seg;
+    p->solve_forced = form;  // from the next input upload on
     p->lag_srs = nullptr;
     if (flags & PLONK_PROVER_LAGRANGE_COMMITS) PLONK_TRY(msm_lagrange_srs(p->circuit.ctx, p->circuit.srs, p->circuit.log_n, &p->lag_srs));
     return PLONK_OK;

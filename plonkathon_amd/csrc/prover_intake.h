@@ -13,6 +13,7 @@
 //   inputs, async              H: wait inputs.read (if pending) · H2D inputs · record ev_copied
 //                              C: wait ev_copied · SOLVE · GATHER
 //   SOLVE  = memset bad_input · witness_seed_kernel · record inputs.read · [prof] witness_solve_kernel [prof]
+//            (the levelised form, solve_form_of: witness_solve_levels_kernel in that kernel's place)
 //   GATHER = witness_scatter_kernel · public_gather_kernel (if n_public) · PI column · record vars.read
 //   PI column = memset (n_public == 0) | pi_fill_kernel (dense PI) | nothing (sparse PI: round 1 builds it from pub)
 // The solver writes `vars` in place: on C it is behind the previous batch's gathers, the only readers, so only the staging buffer
@@ -62,7 +63,8 @@ static int intake_init(plonk_prover* p, const uint8_t* selectors_le32) {
 }
 static void intake_destroy(plonk_prover* p) {
     dev_free_all({(void**)&p->intake.vars.buf, (void**)&p->intake.inputs.buf, (void**)&p->intake.bad_input, (void**)&p->wiring.cell_index,
-                  (void**)&p->wiring.pub_index, (void**)&p->solver.desc, (void**)&p->solver.input_index, (void**)&p->solver.bad});
+                  (void**)&p->wiring.pub_index, (void**)&p->solver.desc, (void**)&p->solver.order, (void**)&p->solver.level_start,
+                  (void**)&p->solver.input_index, (void**)&p->solver.bad});
     for (hipEvent_t ev : {p->intake.vars.read, p->intake.inputs.read, p->intake.ev_copied})  // each exists only if an upload created it
         if (ev) hipEventDestroy(ev);
     free(p->solver.gates_host);
@@ -94,6 +96,12 @@ static int fill_pi_column(plonk_prover* p, size_t B) {
     else if (!p->circuit.sparse_pi) PLONK_LAUNCH(pi_fill_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)p->intake.pub, l, n, B, pi);
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
+}
+
+// the form of the solve of B proofs: PLONK_PROVER_SOLVE_FORM where it was set, the automatic rule otherwise
+static unsigned solve_form_of(const plonk_prover* p, size_t B) {
+    const plonk_prover::Solver& sv = p->solver;
+    return p->solve_forced ? p->solve_forced : solve_plan_form(device_cus(p->circuit.ctx->device), sv.active, sv.steps, sv.threads, B);
 }
 
 // Per-variable values of a batch, uploaded ([B][n_vars] canonical LE, n_vars * 32 bytes per proof instead of 3 * n * 32) or, from_inputs,
@@ -129,8 +137,13 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
         PLONK_CHECK_HIP(hipEventRecord(in.inputs.read, s));
         in.inputs.read_pending = true;
         PLONK_TRY(prof_begin(ctx, "witness_solve", 32.0 * (double)V * (double)B));
-        PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
-                     (const uint32_t*)p->wiring.cell_index, (const Fr*)p->circuit.fixed_lag, V, n, p->solver.rows, B, p->solver.bad);
+        if (solve_form_of(p, B) == PLONK_PROVER_SOLVE_LEVELS)
+            PLONK_LAUNCH(witness_solve_levels_kernel, dim3((unsigned)B), dim3(p->solver.threads), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
+                         (const uint32_t*)p->solver.order, (const uint32_t*)p->solver.level_start, (const uint32_t*)p->wiring.cell_index,
+                         (const Fr*)p->circuit.fixed_lag, V, n, p->solver.levels, p->solver.bad);
+        else
+            PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
+                         (const uint32_t*)p->wiring.cell_index, (const Fr*)p->circuit.fixed_lag, V, n, p->solver.rows, B, p->solver.bad);
         PLONK_TRY(prof_end(ctx));
     } else if (async) {
         PLONK_TRY(staging_copy(p, &in.vars, src_le32, B * V * sizeof(Fr), true));
@@ -196,7 +209,8 @@ int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const u
     PLONK_REQUIRE(w.cell_host, PLONK_ERR_NOMEM, "out of host memory");
     memcpy(w.cell_host, cell_index, cells * sizeof(uint32_t));
     w.n_vars = n_vars;
-    p->solver.n_inputs = 0;  // a plan belongs to the wiring it was built from
+    p->solver.n_inputs = 0;  // a plan belongs to the wiring it was built from: it goes, with its schedule
+    dev_free_all({(void**)&p->solver.desc, (void**)&p->solver.order, (void**)&p->solver.level_start});
     p->intake.vars_valid = false;
     return PLONK_OK;
 }
@@ -214,19 +228,30 @@ int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(p->wiring.n_vars && p->wiring.cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
     plonk_prover::Solver& sv = p->solver;
-    std::vector<uint32_t> desc;
-    PLONK_TRY(solve_plan_build(sv.gates_host, p->wiring.cell_host, p->circuit.n, p->wiring.n_vars, input_index, n_inputs, desc, out_missing_var));
+    SolvePlan plan;
+    PLONK_TRY(solve_plan_build(sv.gates_host, p->wiring.cell_host, p->circuit.n, p->wiring.n_vars, input_index, n_inputs, plan, out_missing_var));
+    const std::vector<uint32_t>& desc = plan.desc;
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // a batch in flight still walks the old plan
     sv.n_inputs = 0;
     p->intake.resident_b = 0;
-    dev_free_all({(void**)&sv.desc, (void**)&sv.input_index, (void**)&p->intake.inputs.buf, (void**)&sv.bad});
+    dev_free_all({(void**)&sv.desc, (void**)&sv.order, (void**)&sv.level_start, (void**)&sv.input_index, (void**)&p->intake.inputs.buf, (void**)&sv.bad});
     p->intake.inputs.cap = 0;
     PLONK_TRY(dev_alloc((void**)&sv.desc, desc.size() * sizeof(uint32_t)));
+    PLONK_TRY(dev_alloc((void**)&sv.order, plan.order.size() * sizeof(uint32_t)));
+    PLONK_TRY(dev_alloc((void**)&sv.level_start, plan.level_start.size() * sizeof(uint32_t)));
     PLONK_TRY(dev_alloc((void**)&sv.input_index, n_inputs * sizeof(uint32_t)));
+    if (!plan.order.empty())
+        PLONK_CHECK_HIP(hipMemcpyAsync(sv.order, plan.order.data(), plan.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PLONK_CHECK_HIP(hipMemcpyAsync(sv.level_start, plan.level_start.data(), plan.level_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     if (!desc.empty()) PLONK_CHECK_HIP(hipMemcpyAsync(sv.desc, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     PLONK_CHECK_HIP(hipMemcpyAsync(sv.input_index, input_index, n_inputs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     sv.rows = (uint32_t)desc.size();
+    sv.active = (uint32_t)plan.order.size();
+    sv.levels = (uint32_t)plan.level_start.size() - 1;
+    sv.widest = plan.widest;
+    sv.threads = plan.threads;
+    sv.steps = plan.steps;
     sv.n_inputs = n_inputs;
     return PLONK_OK;
 }
@@ -273,6 +298,20 @@ int plonk_prover_solve_failures(plonk_prover* p, size_t B, uint32_t* out_rows) {
     }
     PLONK_CHECK_HIP(hipMemcpyAsync(out_rows, p->solver.bad, B * sizeof(uint32_t), hipMemcpyDeviceToHost, p->circuit.ctx->stream));
     PLONK_CHECK_HIP(hipStreamSynchronize(p->circuit.ctx->stream));
+    return PLONK_OK;
+}
+
+// DIAGNOSTICS: the solver's plan and what the rule makes of it for `batch` proofs: out = rows walked, active rows, levels, the
+// widest level, T (the levelised kernel's block), the form solve_plan_form picks (1 = one lane per proof, 2 = levels), and the
+// levelised form's steps
+int plonk_prover_solve_plan(plonk_prover* p, size_t batch, uint32_t out[7]) {
+    PLONK_REQUIRE(p && batch && out, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(p->circuit.ctx);
+    const plonk_prover::Solver& sv = p->solver;
+    PLONK_REQUIRE(sv.n_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
+    const uint32_t plan[7] = {sv.rows, sv.active, sv.levels, sv.widest, sv.threads,
+                              solve_plan_form(device_cus(p->circuit.ctx->device), sv.active, sv.steps, sv.threads, batch), sv.steps};
+    memcpy(out, plan, sizeof plan);
     return PLONK_OK;
 }
 

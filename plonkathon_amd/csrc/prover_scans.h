@@ -413,6 +413,35 @@ unsigned prover_plan_segments(unsigned cus, unsigned log_n, size_t B) {
     return S;
 }
 
+// Which form the witness solve of `B` proofs takes (witness_solve.h): PLONK_PROVER_SOLVE_LANES, one lane per proof walking the `active`
+// rows in program order, or PLONK_PROVER_SOLVE_LEVELS, one workgroup of `threads` lanes per proof walking `steps` = sum over the
+// dependency levels of ceil(width / threads) steps, each a row and a workgroup barrier.  Both are chains of dependent loads, so a
+// launch costs its serial steps times the rounds the chip needs to hold every wave of it:
+//     lanes    active x SOLVE_ROW_NS             x ceil(ceil(B / 64) / (cus x SOLVE_WAVES_PER_CU))
+//     levels   steps  x SOLVE_LEVEL_STEP[_WIDE]_NS x ceil(B x threads / 64 / (cus x SOLVE_WAVES_PER_CU))
+// Measured on an MI355X (profiles/witness_levels.json, tools/witness_levels_bench.py; the table is in DESIGN.md 4.3).  The three
+// step costs are fitted on the B = 1 cells, where nothing but the chain of steps is timed: a row of the one-lane form costs
+// 1.16 - 1.41 us over the four circuits (median 1.23); a level step 1.40 - 1.47 us (median 1.45) where the workgroup is one wave (T = 64: the barrier is nearly
+// free) and 2.15 us where it is four (T = 256, poseidon_multi(64)).  SOLVE_WAVES_PER_CU is not a measurement: both kernels compile to
+// 7 waves per SIMD (profiles/witness_levels_kernel_resource_usage.txt), and no batch of the table fills the chip with them.  A
+// level step costs more than a row step, so a circuit whose levels are one row wide (steps == active: a chain) keeps the one-lane
+// form for every B.  With these the rule's pick is the faster forced form in all 16 measured cells.
+// NOT measured: the rule models one prover alone on the chip.  The levelised form holds threads / 64 waves per proof where the
+// one-lane form holds 1 / 64 of a wave, so under several contexts proving at once (bench.py's 20 streams) its shorter latency is
+// bought with wave slots the other streams' kernels could use; the multi-stream step from inputs (tools/witness_bench.py part b) has
+// been measured on the chain only, which stays on the one-lane form.  No measured cell has rounds > 1 either.
+#define SOLVE_ROW_NS 1231.0
+#define SOLVE_LEVEL_STEP_NS 1454.0
+#define SOLVE_LEVEL_STEP_WIDE_NS 2147.0
+#define SOLVE_WAVES_PER_CU 28
+unsigned solve_plan_form(unsigned cus, uint32_t active, uint32_t steps, uint32_t threads, size_t B) {
+    const size_t slots = (size_t)(cus ? cus : 1) * SOLVE_WAVES_PER_CU;
+    auto rounds = [slots](size_t waves) { return (double)((waves + slots - 1) / slots); };
+    const double lanes = (double)active * SOLVE_ROW_NS * rounds((B + 63) / 64);
+    const double levels = (double)steps * (threads > 64 ? SOLVE_LEVEL_STEP_WIDE_NS : SOLVE_LEVEL_STEP_NS) * rounds(B * (threads / 64));
+    return levels < lanes ? PLONK_PROVER_SOLVE_LEVELS : PLONK_PROVER_SOLVE_LANES;
+}
+
 // The scratch of the segmented scans, `seg`: the carries and partial sums of the S segments of B proofs, none while S = 1.  The
 // three families follow each other on one stream and share it from its start: the evaluations' seven partial sums per segment
 // are the largest (7 B S), the grand product takes 2 B S + B (numerator carries, denominator carries, the proofs' inversions), the
