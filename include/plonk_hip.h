@@ -302,6 +302,31 @@ int plonk_prover_upload_inputs(plonk_prover* p, const uint8_t* inputs_le32, size
 int plonk_prover_upload_inputs_async(plonk_prover* p, const uint8_t* inputs_le32, size_t batch);
 int plonk_prover_download_variables(plonk_prover* p, size_t batch, const uint32_t* var_index, size_t k, uint8_t* out_le32);
 int plonk_prover_solve_failures(plonk_prover* p, size_t batch, uint32_t* out_rows);
+/* Two-slot intake: the NEXT batch is staged while the resident one proves.  A prover that stages owns a second set of intake buffers
+ * (wire columns [4][batch][n], variables [batch][n_vars], inputs, verdicts: allocated by the first stage, never otherwise, freed by
+ * plonk_prover_destroy).  Staging copies the bytes, seeds and solves them (or converts and range-checks packed variables) and gathers
+ * wire columns, public inputs and the PI column into that set, all on the context's copy stream; nothing of the resident batch is
+ * read or written.
+ *   plonk_prover_stage_inputs     inputs_le32 as plonk_prover_upload_inputs_async takes them; the solve has the form an upload of
+ *                         `batch` proofs would have.
+ *   plonk_prover_stage_variables  vars_le32 as plonk_prover_upload_variables_async takes them.
+ *   plonk_prover_staged   *out_batch = the staged batch, 0: nothing is staged.
+ *   plonk_prover_advance  the compute stream waits for the stage, the staged batch becomes the resident one (by pointer: the former
+ *                         resident set is what the next stage fills); *out_batch = its size, the `batch` of run and download.
+ * Contract.  Stage never waits on the host, unless a staged buffer has to grow: then for the copy stream and for the last reader of
+ * that set, never for the compute stream.  The caller keeps the source alive until plonk_prover_advance returns; page-locked memory
+ * (plonk_host_alloc) for a copy that overlaps.  Per batch: stage(k + 1) any time after batch k became resident, run(k), download(k),
+ * advance(), run(k + 1).  advance before download(k) is allowed and gives up batch k's results.  PLONK_ERR_STATE: a stage while a batch
+ * is staged; advance with nothing staged; stage_inputs before plonk_prover_set_inputs; stage_* before plonk_prover_set_wiring;
+ * plonk_prover_set_wiring / plonk_prover_set_inputs with a batch staged (the plan it was solved under would change).  A plain
+ * plonk_prover_upload_* with a batch staged replaces the resident batch and leaves the staged one alone.  The staged batch's verdicts —
+ * status bits 3 and 4, plonk_prover_solve_failures — and its variables (plonk_prover_download_variables) become visible only after
+ * advance: until then every read is of the resident batch.  A staged batch larger than any before grows the staged set at the stage
+ * and the rounds' own buffers at advance.                                                                                          */
+int plonk_prover_stage_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t batch);
+int plonk_prover_stage_variables(plonk_prover* p, const uint8_t* vars_le32, size_t batch);
+int plonk_prover_staged(const plonk_prover* p, size_t* out_batch); /* 0: nothing staged */
+int plonk_prover_advance(plonk_prover* p, size_t* out_batch);
 int plonk_prover_run(plonk_prover* p, size_t batch);
 int plonk_prover_download(plonk_prover* p, size_t batch, uint8_t* out_proofs, uint8_t* out_status);
 int plonk_prover_challenges(plonk_prover* p, size_t b, uint8_t out_le32[6 * 32]);

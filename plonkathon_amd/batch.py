@@ -68,6 +68,7 @@ class BatchProver:
         check(self.ctx.L.plonk_prover_create(self.ctx.handle, self._bases.handle, _log2_exact(n), sel,
                                              len(self._public_vars), ctypes.byref(self._h)))
         self._resident = 0
+        self._staged_source = None  # the bytes of a staged batch: the library reads them until `advance`
         flags = 1 if lagrange_commits else 0
         if segments is not None:
             if segments < 1 or segments & (segments - 1):
@@ -205,6 +206,52 @@ class BatchProver:
         check(self.ctx.L.plonk_prover_upload_inputs_async(self._h, ctypes.addressof(pinned), B))
         self._resident = B
 
+    # ---- two-slot intake: the next batch is staged on the copy stream while the resident one proves -----------------
+    def stage_inputs(self, assignments):
+        """`upload_inputs` into the prover's second intake slot: the batch is copied, solved and gathered on the context's copy
+        stream, beside whatever the resident batch is doing, and becomes the resident one at `advance()`.  Nothing of the resident
+        batch changes: `run`, `download`, `variable_values`, `public_values` and `solve_failures` keep meaning it."""
+        if self._input_keys is None:
+            self.set_inputs(list(assignments[0]))
+        B = len(assignments)
+        enc = _pack_witnesses(assignments, self._input_keys, R_MOD)
+        check(self.ctx.L.plonk_prover_stage_inputs(self._h, enc, B))
+        self._staged_source = enc
+
+    def stage_input_values_async(self, pinned, B):
+        """`stage_inputs` from packed bytes without a host wait: `pinned` = a Context.host_alloc buffer holding [B][K] canonical
+        32-byte values in the order of `self.inputs`, untouched until `advance()` has returned.  A non-canonical value shows up as
+        status bit 3 of the batch once it is resident."""
+        K = len(self._input_keys or ())
+        if self._input_keys is not None and len(pinned) < 32 * B * K:
+            raise ValueError("stage_input_values_async: expected %d bytes" % (32 * B * K))
+        check(self.ctx.L.plonk_prover_stage_inputs(self._h, ctypes.addressof(pinned), B))
+        self._staged_source = pinned
+
+    def stage_values_async(self, pinned, B):
+        """The same for packed variables, as `upload_values_async`: `pinned` holds [B][V] canonical 32-byte values in the order of
+        `self.variables`."""
+        if len(pinned) < 32 * B * len(self._vars):
+            raise ValueError("stage_values_async: expected %d bytes" % (32 * B * len(self._vars)))
+        check(self.ctx.L.plonk_prover_stage_variables(self._h, ctypes.addressof(pinned), B))
+        self._staged_source = pinned
+
+    @property
+    def staged(self):
+        """The size of the batch that is staged, 0 if none is."""
+        out = ctypes.c_size_t(0)
+        check(self.ctx.L.plonk_prover_staged(self._h, ctypes.byref(out)))
+        return out.value
+
+    def advance(self):
+        """The staged batch becomes the resident one (the compute stream waits for its staging; no host wait); returns its size.
+        The batch that was resident is given up, downloaded or not."""
+        out = ctypes.c_size_t(0)
+        check(self.ctx.L.plonk_prover_advance(self._h, ctypes.byref(out)))
+        self._resident = out.value
+        self._staged_source = None
+        return out.value
+
     def variable_values(self, names=None, B=None):
         """The resident batch's variable values, one dict name -> int per proof (all variables, or `names`): what the
         solver computed, after `upload_inputs*`; what was uploaded, after `upload` / `upload_values*`."""
@@ -328,6 +375,24 @@ class BatchProver:
         self.upload_inputs(assignments)
         self.run()
         return self.download()
+
+    def prove_inputs_stream(self, batches):
+        """`prove_inputs` over an iterable of batches, as a generator of each batch's proofs in order: batch k + 1 is packed and
+        staged (`stage_inputs`) right after batch k's rounds were enqueued, so that its copy and its solve run beside them, and
+        batch k is downloaded after that."""
+        batches = iter(batches)
+        batch = next(batches, None)
+        if batch is None:
+            return
+        self.upload_inputs(batch)
+        while batch is not None:
+            self.run()
+            batch = next(batches, None)
+            if batch is not None:
+                self.stage_inputs(batch)
+            yield self.download()
+            if batch is not None:
+                self.advance()
 
     def prove(self, witness) -> Proof:  # prover.py:51-84
         return self.prove_batch([witness])[0]

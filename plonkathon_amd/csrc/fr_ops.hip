@@ -37,12 +37,15 @@ __global__ void fr_to_mont_checked_kernel(const Fr* in, Fr* out, size_t n, unsig
 }
 
 // in-place Montgomery conversion of freshly uploaded values; *first_bad = index of the first element >= r, or ~0
-int k_fr_to_mont_checked(plonk_ctx* ctx, Fr* data, size_t n, unsigned long long* d_first_bad) {
+int k_fr_to_mont_checked_on(hipStream_t stream, Fr* data, size_t n, unsigned long long* d_first_bad) {
     if (!n) return PLONK_OK;
-    PLONK_CHECK_HIP(hipMemsetAsync(d_first_bad, 0xff, sizeof(unsigned long long), ctx->stream));
-    PLONK_LAUNCH(fr_to_mont_checked_kernel, grid_for(n), dim3(256), 0, ctx->stream, (const Fr*)data, data, n, d_first_bad);
+    PLONK_CHECK_HIP(hipMemsetAsync(d_first_bad, 0xff, sizeof(unsigned long long), stream));
+    PLONK_LAUNCH(fr_to_mont_checked_kernel, grid_for(n), dim3(256), 0, stream, (const Fr*)data, data, n, d_first_bad);
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
+}
+int k_fr_to_mont_checked(plonk_ctx* ctx, Fr* data, size_t n, unsigned long long* d_first_bad) {
+    return k_fr_to_mont_checked_on(ctx->stream, data, n, d_first_bad);
 }
 
 int k_fr_to_mont(plonk_ctx* ctx, const Fr* in, Fr* out, size_t n) {

@@ -203,6 +203,7 @@ int prof_end(plonk_ctx* ctx);
 int k_fr_to_mont(plonk_ctx*, const Fr* in, Fr* out, size_t n);
 int k_fr_from_mont(plonk_ctx*, const Fr* in, Fr* out, size_t n);
 int k_fr_to_mont_checked(plonk_ctx*, Fr* data, size_t n, unsigned long long* d_first_bad);
+int k_fr_to_mont_checked_on(hipStream_t stream, Fr* data, size_t n, unsigned long long* d_first_bad);  // the same on a stream given (the copy stream: a staged batch)
 int k_fr_pointwise(plonk_ctx*, int op, const Fr* a, const Fr* b, Fr* out, size_t n);
 int k_fr_pointwise_scalar(plonk_ctx*, int op, const Fr* a, const Fr& s_mont, Fr* out, size_t n, size_t limit);
 int k_fr_batch_inverse(plonk_ctx*, const Fr* in, Fr* out, size_t n);

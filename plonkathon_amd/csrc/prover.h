@@ -52,6 +52,24 @@ struct Staging {
     bool read_pending;  // `read` has been recorded: the next asynchronous copy into buf waits for it
 };
 
+// The second intake slot (prover_intake.h: stage, advance): everything a batch owns before the rounds run, for the ONE batch that is
+// staged on the copy stream while the resident one proves.  plonk_prover_advance swaps these with the resident batch's (Rounds::wit_lag,
+// the Intake fields of the same names, Solver::bad and Solver::valid).  All null until the first stage.
+struct StagedSlot {
+    size_t batch;              // the staged batch, 0: none
+    size_t cap_b;              // proofs that wit_lag and pub hold
+    Fr* wit_lag;               // [4][B][n]
+    Fr* pub;                   // [B][n_public]
+    Staging vars, inputs;      // as Intake's; their `read` events travel with the buffers
+    unsigned long long* bad_input;
+    size_t bad_stride;
+    uint32_t* solve_bad;       // [B] (capacity: inputs.cap proofs, as Solver::bad)
+    bool solved;               // the staged batch came through the solver
+    hipEvent_t ready;          // recorded on the copy stream behind the stage's last kernel: advance makes the compute stream wait for it
+    hipEvent_t released;       // recorded on the compute stream by advance, behind the last reader of the buffers that became this slot's
+    bool released_pending;     // the next stage waits for `released` first
+};
+
 struct plonk_prover {
     // ---- the circuit: set by plonk_prover_create, constant afterwards
     struct Circuit {
@@ -109,6 +127,7 @@ struct plonk_prover {
     // ---- intake and staging (prover_intake.h): the batch that is resident, and how its bytes came in
     struct Intake {
         size_t resident_b;         // batch size of the witnesses currently resident (run / download must match it)
+        size_t cap_b;              // proofs that rounds.wit_lag and pub hold: rounds.cap_b, until an advance brings the other slot's buffers in
         Fr* pub;                   // [B][n_public]   public inputs of the resident batch (Montgomery); a per-batch buffer
         Staging vars;              // [B][n_vars] values of the resident batch (Montgomery); cap in elements; read by the gathers
         Staging inputs;            // [B][n_inputs] the uploaded input values (canonical, as copied); cap in proofs; read by the seed
@@ -117,6 +136,7 @@ struct plonk_prover {
         unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
         size_t bad_stride;         // values per proof of the last upload that ran the checked conversion: *bad_input / bad_stride owns the bad value
     } intake;
+    StagedSlot staged;             // the batch behind the resident one (plonk_prover_stage_*, plonk_prover_advance)
     // ---- the witness solver (witness_solve.h; plonk_prover_set_inputs, plonk_prover_upload_inputs)
     struct Solver {
         uint8_t* gates_host;       // [5][n] canonical LE: QM, QL, QR, QO, QC as plonk_prover_create was given them

@@ -355,23 +355,29 @@ static unsigned prover_segments(const plonk_prover* p, size_t B) {
 }
 
 // The per-batch buffers, once: what ensure_batch allocates, free_batch frees and the out-of-memory message adds up.  Per proof a buffer
-// holds n_vectors Fr vectors of n elements and `bytes` more; `extra` bytes once.
-struct BatchBuffer { void** slot; size_t n_vectors, bytes, extra; };
+// holds n_vectors Fr vectors of n elements and `bytes` more; `extra` bytes once.  in_set: the buffer belongs to the resident batch's set
+// (prover_intake.h): an advance exchanges it with the staged set's, which staged_grow sizes on its own.
+struct BatchBuffer { void** slot; size_t n_vectors, bytes, extra; bool in_set; };
 #define BATCH_N_VECTORS 32  // 32 n-vectors of 32 bytes per proof: the figure of the out-of-memory message
 static std::array<BatchBuffer, 13> batch_buffers(plonk_prover* p) {
     plonk_prover::Rounds& r = p->rounds;
     plonk_prover::Results& o = p->results;
     const size_t e = sizeof(Fr);
-    return {{{(void**)&r.wit_lag, 4}, {(void**)&r.z_lag, 1}, {(void**)&r.coef, 5}, {(void**)&r.big, 5 * QCOSETS}, {(void**)&r.quot, 4},
+    return {{{(void**)&r.wit_lag, STAGED_N_VECTORS, 0, 0, true}, {(void**)&r.z_lag, 1}, {(void**)&r.coef, 5}, {(void**)&r.big, 5 * QCOSETS}, {(void**)&r.quot, 4},
              {(void**)&r.num, 1}, {(void**)&r.wz, 2}, {(void**)&r.closes, 0, 2 * sizeof(uint32_t)}, {(void**)&r.lin_w, 0, sizeof(LinWeights)},
              {(void**)&o.commit_xy, 0, PROOF_POINTS * 2 * sizeof(Fq)}, {(void**)&o.commit_flags, 0, PROOF_POINTS},
-             {(void**)&o.state, 0, sizeof(ProofState)}, {(void**)&p->intake.pub, 0, p->circuit.n_public * e, e}}};
+             {(void**)&o.state, 0, sizeof(ProofState)}, {(void**)&p->intake.pub, 0, p->circuit.n_public * e, e, true}}};
 }
 
-static void free_batch(plonk_prover* p) {
-    for (const BatchBuffer& b : batch_buffers(p)) dev_free_all({b.slot});
-    dev_free_all({(void**)&p->rounds.seg, (void**)&p->intake.vars.buf});  // sized by the batch too: they make room for a larger one
-    p->rounds.seg_cap = p->intake.vars.cap = p->intake.resident_b = p->rounds.cap_b = 0;
+// all of them, or (rounds_only) all but the resident set's
+static void free_batch(plonk_prover* p, bool rounds_only = false) {
+    for (const BatchBuffer& b : batch_buffers(p))
+        if (!(rounds_only && b.in_set)) dev_free_all({b.slot});
+    dev_free_all({(void**)&p->rounds.seg});  // sized by the batch too: it makes room for a larger one
+    p->rounds.seg_cap = p->intake.resident_b = p->rounds.cap_b = 0;
+    if (rounds_only) return;
+    dev_free_all({(void**)&p->intake.vars.buf});  // the same
+    p->intake.vars.cap = p->intake.cap_b = 0;
 }
 
 // the carries and partial sums of the segmented scans (prover_scans.h: scan_scratch_elems)
@@ -380,27 +386,31 @@ static int ensure_segments(plonk_prover* p, size_t B) {
     return dev_grow(p->circuit.ctx->stream, &p->rounds.seg_cap, need, {{(void**)&p->rounds.seg, need * sizeof(Fr)}});
 }
 
-static int ensure_batch(plonk_prover* p, size_t B) {
-    if (B <= p->rounds.cap_b) return ensure_segments(p, B);
+// The per-batch buffers (rounds_only: as free_batch) for B proofs: nothing while they hold B, otherwise all of them anew.
+static int ensure_buffers(plonk_prover* p, size_t B, bool rounds_only) {
+    if (B <= p->rounds.cap_b && (rounds_only || B <= p->intake.cap_b)) return ensure_segments(p, B);
     PLONK_CHECK_HIP(hipStreamSynchronize(p->circuit.ctx->stream));
-    free_batch(p);
+    free_batch(p, rounds_only);
     int rc = PLONK_OK;
     size_t vectors = 0;
     for (const BatchBuffer& b : batch_buffers(p)) {
-        if (rc == PLONK_OK) rc = dev_alloc(b.slot, B * (b.n_vectors * p->circuit.n * sizeof(Fr) + b.bytes) + b.extra);
+        if (rc == PLONK_OK && !(rounds_only && b.in_set)) rc = dev_alloc(b.slot, B * (b.n_vectors * p->circuit.n * sizeof(Fr) + b.bytes) + b.extra);
         vectors += b.n_vectors;
     }
     assert(vectors == BATCH_N_VECTORS);
     if (rc != PLONK_OK) {
-        free_batch(p);
+        free_batch(p, rounds_only);
         if (rc == PLONK_ERR_NOMEM)
             plonk_set_error("a batch of %zu proofs of group_order %zu needs %zu bytes of device memory", B, p->circuit.n,
                             BATCH_N_VECTORS * B * p->circuit.n * sizeof(Fr));
         return rc;
     }
     p->rounds.cap_b = B;
+    if (!rounds_only) p->intake.cap_b = B;
     return ensure_segments(p, B);
 }
+static int ensure_batch(plonk_prover* p, size_t B) { return ensure_buffers(p, B, false); }
+static int ensure_rounds(plonk_prover* p, size_t B) { return ensure_buffers(p, B, true); }
 
 // One transcript round of every proof: round 0 opens the transcripts, round r absorbs what round r of the prover produced.
 static void transcript_round(plonk_prover* p, size_t B, int round) {
@@ -538,6 +548,7 @@ int plonk_prover_destroy(plonk_prover* p) {
     if (c.ctx) {
         plonk_use_device(c.ctx->device);
         hipStreamSynchronize(c.ctx->stream);
+        if (c.ctx->copy_stream) hipStreamSynchronize(c.ctx->copy_stream);  // a batch that is still staged: its solve reads the circuit and the plan
     }
     free_batch(p);
     dev_free_all({(void**)&c.fixed_lag, (void**)&c.fixed_coef, (void**)&c.fixed_big, (void**)&c.l0_big, (void**)&c.x_big, (void**)&c.g_pow,

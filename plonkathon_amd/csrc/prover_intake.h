@@ -18,12 +18,28 @@
 //   PI column = memset (n_public == 0) | pi_fill_kernel (dense PI) | nothing (sparse PI: round 1 builds it from pub)
 // The solver writes `vars` in place: on C it is behind the previous batch's gathers, the only readers, so only the staging buffer
 // that H writes needs its `read` event.  An async path's canonical-range verdict comes back as PROVER_ST_BAD_INPUT of the download.
+//
+// The second slot (StagedSlot, prover.h).  A prover that stages owns a second wit_lag, pub, vars, inputs, bad_input and solver.bad.  The
+// uploads above fill the RESIDENT set on C; a stage fills the STAGED set on H alone, where copy, seed, solve and gathers are in order
+// without an event between them, and touches nothing of the resident batch:
+//   stage inputs               H: wait released (if pending) · H2D inputs · SOLVE (no record, no prof) · GATHER (no record) · record ready
+//   stage variables            H: wait released (if pending) · H2D vars · checked conversion in place [memset bad_input, kernel]
+//                                 · GATHER (no record) · record ready
+//   advance                    C: wait ready · [host: the two sets change places by pointer] · record released
+// `released` stands behind everything C was given while the buffers that are now the staged set were resident — the rounds that read
+// wit_lag and pub, the download that reads the two verdicts — so it is all the next stage waits for.  Growing a staged buffer waits on
+// the host for H and for `released`, never for C; growing the rounds' buffers for a staged batch larger than any before is left to
+// advance, which gives up the resident batch anyway.
 #pragma once
 #include <string.h>
 
+#include <utility>
+
 #include "witness_solve.h"  // prover.h; the plan, the solver's kernels
 
-static int ensure_batch(plonk_prover* p, size_t B);  // prover.hip: the per-batch buffers of B proofs
+static int ensure_batch(plonk_prover* p, size_t B);   // prover.hip: the per-batch buffers of B proofs, the resident set's among them
+static int ensure_rounds(plonk_prover* p, size_t B);  // prover.hip: the same without the resident set's (advance brings its own)
+#define STAGED_N_VECTORS 4  // n-vectors per proof of a set (wit_lag); BATCH_N_VECTORS counts them for the resident one
 
 // witness upload helper: PI[b][i] = -public[b][i] for i < n_public, 0 otherwise (prover.py:57-62)
 __global__ void pi_fill_kernel(const Fr* pub, size_t n_public, size_t n, size_t B, Fr* pi) {
@@ -65,8 +81,10 @@ static void intake_destroy(plonk_prover* p) {
     dev_free_all({(void**)&p->intake.vars.buf, (void**)&p->intake.inputs.buf, (void**)&p->intake.bad_input, (void**)&p->wiring.cell_index,
                   (void**)&p->wiring.pub_index, (void**)&p->solver.desc, (void**)&p->solver.order, (void**)&p->solver.level_start,
                   (void**)&p->solver.input_index, (void**)&p->solver.bad});
-    for (hipEvent_t ev : {p->intake.vars.read, p->intake.inputs.read, p->intake.ev_copied})  // each exists only if an upload created it
-        if (ev) hipEventDestroy(ev);
+    StagedSlot& sl = p->staged;  // a batch still staged goes with its buffers (plonk_prover_destroy has waited for both streams)
+    dev_free_all({(void**)&sl.wit_lag, (void**)&sl.pub, (void**)&sl.vars.buf, (void**)&sl.inputs.buf, (void**)&sl.bad_input, (void**)&sl.solve_bad});
+    for (hipEvent_t ev : {p->intake.vars.read, p->intake.inputs.read, p->intake.ev_copied, sl.vars.read, sl.inputs.read, sl.ready, sl.released})
+        if (ev) hipEventDestroy(ev);  // each exists only if an upload or a stage created it
     free(p->solver.gates_host);
     free(p->wiring.cell_host);
 }
@@ -87,13 +105,12 @@ static int staging_copy(plonk_prover* p, Staging* st, const uint8_t* src, size_t
     return PLONK_OK;
 }
 
-// the PI column of the B uploaded witnesses, wit_lag[3]: -public inputs, then zeros (the sparse form is built from `pub` in round 1)
-static int fill_pi_column(plonk_prover* p, size_t B) {
+// the PI column of B witnesses, wit_lag[3]: -public inputs, then zeros (the sparse form is built from `pub` in round 1)
+static int fill_pi_column(plonk_prover* p, Fr* wit_lag, const Fr* pub, size_t B, hipStream_t s) {
     const size_t n = p->circuit.n, l = p->circuit.n_public;
-    hipStream_t s = p->circuit.ctx->stream;
-    Fr* pi = p->rounds.wit_lag + 3 * B * n;
+    Fr* pi = wit_lag + 3 * B * n;
     if (!l) PLONK_CHECK_HIP(hipMemsetAsync(pi, 0, B * n * sizeof(Fr), s));
-    else if (!p->circuit.sparse_pi) PLONK_LAUNCH(pi_fill_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)p->intake.pub, l, n, B, pi);
+    else if (!p->circuit.sparse_pi) PLONK_LAUNCH(pi_fill_kernel, grid1(B * n), dim3(256), 0, s, pub, l, n, B, pi);
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
 }
@@ -102,6 +119,39 @@ static int fill_pi_column(plonk_prover* p, size_t B) {
 static unsigned solve_form_of(const plonk_prover* p, size_t B) {
     const plonk_prover::Solver& sv = p->solver;
     return p->solve_forced ? p->solve_forced : solve_plan_form(device_cus(p->circuit.ctx->device), sv.active, sv.steps, sv.threads, B);
+}
+
+// One batch's own buffers, wherever they live: the resident set or the staged one.
+struct BatchSet { Fr *wit_lag, *pub, *vars, *inputs; unsigned long long* bad_input; uint32_t* solve_bad; };
+static BatchSet resident_set(plonk_prover* p) {
+    return {p->rounds.wit_lag, p->intake.pub, p->intake.vars.buf, p->intake.inputs.buf, p->intake.bad_input, p->solver.bad};
+}
+static BatchSet staged_set(plonk_prover* p) {
+    const StagedSlot& sl = p->staged;
+    return {sl.wit_lag, sl.pub, sl.vars.buf, sl.inputs.buf, sl.bad_input, sl.solve_bad};
+}
+
+// The three steps that SOLVE and GATHER (the head of this file) are made of, for B proofs of the set `bs` on stream s.
+static void enqueue_seed(plonk_prover* p, const BatchSet& bs, size_t B, hipStream_t s) {
+    const size_t V = p->wiring.n_vars, K = p->solver.n_inputs;
+    PLONK_LAUNCH(witness_seed_kernel, grid1(B * K), dim3(256), 0, s, (const Fr*)bs.inputs, (const uint32_t*)p->solver.input_index, K, V, B, bs.vars,
+                 bs.bad_input, bs.solve_bad);
+}
+static void enqueue_solve(plonk_prover* p, const BatchSet& bs, size_t B, hipStream_t s) {
+    const size_t n = p->circuit.n, V = p->wiring.n_vars;
+    if (solve_form_of(p, B) == PLONK_PROVER_SOLVE_LEVELS)
+        PLONK_LAUNCH(witness_solve_levels_kernel, dim3((unsigned)B), dim3(p->solver.threads), 0, s, bs.vars, (const uint32_t*)p->solver.desc,
+                     (const uint32_t*)p->solver.order, (const uint32_t*)p->solver.level_start, (const uint32_t*)p->wiring.cell_index,
+                     (const Fr*)p->circuit.fixed_lag, V, n, p->solver.levels, bs.solve_bad);
+    else
+        PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, bs.vars, (const uint32_t*)p->solver.desc,
+                     (const uint32_t*)p->wiring.cell_index, (const Fr*)p->circuit.fixed_lag, V, n, p->solver.rows, B, bs.solve_bad);
+}
+static int enqueue_gather(plonk_prover* p, const BatchSet& bs, size_t B, hipStream_t s) {
+    const size_t n = p->circuit.n, l = p->circuit.n_public, V = p->wiring.n_vars;
+    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.cell_index, V, n, B, bs.wit_lag);
+    if (l) PLONK_LAUNCH(public_gather_kernel, grid1(B * l), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.pub_index, V, l, B, bs.pub);
+    return fill_pi_column(p, bs.wit_lag, bs.pub, B, s);
 }
 
 // Per-variable values of a batch, uploaded ([B][n_vars] canonical LE, n_vars * 32 bytes per proof instead of 3 * n * 32) or, from_inputs,
@@ -118,7 +168,7 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     PLONK_TRY(ensure_batch(p, B));
     plonk_prover::Intake& in = p->intake;
     hipStream_t s = ctx->stream;
-    const size_t n = p->circuit.n, l = p->circuit.n_public, V = p->wiring.n_vars, K = p->solver.n_inputs;
+    const size_t V = p->wiring.n_vars, K = p->solver.n_inputs;
     PLONK_TRY(dev_grow(s, &in.vars.cap, B * V, {{(void**)&in.vars.buf, B * V * sizeof(Fr)}}));
     if (from_inputs) PLONK_TRY(dev_grow(s, &in.inputs.cap, B, {{(void**)&in.inputs.buf, B * K * sizeof(Fr)}, {(void**)&p->solver.bad, B * sizeof(uint32_t)}}));
     if (!in.bad_input) PLONK_TRY(dev_alloc((void**)&in.bad_input, sizeof(unsigned long long)));
@@ -132,18 +182,11 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     if (from_inputs) {
         PLONK_TRY(staging_copy(p, &in.inputs, src_le32, B * K * sizeof(Fr), async));
         PLONK_CHECK_HIP(hipMemsetAsync(in.bad_input, 0xff, sizeof(unsigned long long), s));
-        PLONK_LAUNCH(witness_seed_kernel, grid1(B * K), dim3(256), 0, s, (const Fr*)in.inputs.buf, (const uint32_t*)p->solver.input_index, K, V, B,
-                     in.vars.buf, in.bad_input, p->solver.bad);
+        enqueue_seed(p, resident_set(p), B, s);
         PLONK_CHECK_HIP(hipEventRecord(in.inputs.read, s));
         in.inputs.read_pending = true;
         PLONK_TRY(prof_begin(ctx, "witness_solve", 32.0 * (double)V * (double)B));
-        if (solve_form_of(p, B) == PLONK_PROVER_SOLVE_LEVELS)
-            PLONK_LAUNCH(witness_solve_levels_kernel, dim3((unsigned)B), dim3(p->solver.threads), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
-                         (const uint32_t*)p->solver.order, (const uint32_t*)p->solver.level_start, (const uint32_t*)p->wiring.cell_index,
-                         (const Fr*)p->circuit.fixed_lag, V, n, p->solver.levels, p->solver.bad);
-        else
-            PLONK_LAUNCH(witness_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, in.vars.buf, (const uint32_t*)p->solver.desc,
-                         (const uint32_t*)p->wiring.cell_index, (const Fr*)p->circuit.fixed_lag, V, n, p->solver.rows, B, p->solver.bad);
+        enqueue_solve(p, resident_set(p), B, s);
         PLONK_TRY(prof_end(ctx));
     } else if (async) {
         PLONK_TRY(staging_copy(p, &in.vars, src_le32, B * V * sizeof(Fr), true));
@@ -154,10 +197,7 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     }
     // finish: the wire columns, the public inputs and the PI column from `vars` (vars.read marks its last read); sync: the host waits,
     // and inputs that were only enqueued for their check get their verdict read back
-    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, s, (const Fr*)in.vars.buf, (const uint32_t*)p->wiring.cell_index, V, n, B,
-                 p->rounds.wit_lag);
-    if (l) PLONK_LAUNCH(public_gather_kernel, grid1(B * l), dim3(256), 0, s, (const Fr*)in.vars.buf, (const uint32_t*)p->wiring.pub_index, V, l, B, in.pub);
-    PLONK_TRY(fill_pi_column(p, B));
+    PLONK_TRY(enqueue_gather(p, resident_set(p), B, s));
     PLONK_CHECK_HIP(hipEventRecord(in.vars.read, s));
     in.vars.read_pending = true;
     unsigned long long first_bad = ~0ull;
@@ -170,7 +210,106 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     return PLONK_OK;
 }
 
+// The staged set's buffers for B proofs.  One that is short is freed and allocated anew, after a host wait for H (the previous stage
+// into it) and for `released` (the last reader on C of what is now the staged set) — never for C itself.
+static int staged_grow(plonk_prover* p, size_t B, bool from_inputs) {
+    StagedSlot& sl = p->staged;
+    hipStream_t h = p->circuit.ctx->copy_stream;
+    const size_t n = p->circuit.n, l = p->circuit.n_public, V = p->wiring.n_vars, K = p->solver.n_inputs;
+    if (B > sl.cap_b || B * V > sl.vars.cap || (from_inputs && B > sl.inputs.cap)) {
+        PLONK_CHECK_HIP(hipStreamSynchronize(h));
+        if (sl.released_pending) PLONK_CHECK_HIP(hipEventSynchronize(sl.released));
+        sl.released_pending = false;
+    }
+    int rc = dev_grow(h, &sl.cap_b, B, {{(void**)&sl.wit_lag, 4 * B * n * sizeof(Fr)}, {(void**)&sl.pub, (B * l + 1) * sizeof(Fr)}});
+    if (rc == PLONK_OK) rc = dev_grow(h, &sl.vars.cap, B * V, {{(void**)&sl.vars.buf, B * V * sizeof(Fr)}});
+    if (rc == PLONK_OK && from_inputs)
+        rc = dev_grow(h, &sl.inputs.cap, B, {{(void**)&sl.inputs.buf, B * K * sizeof(Fr)}, {(void**)&sl.solve_bad, B * sizeof(uint32_t)}});
+    if (rc == PLONK_ERR_NOMEM)
+        plonk_set_error("staging a batch of %zu proofs of group_order %zu needs %zu bytes of device memory beside the resident batch's", B, n,
+                        B * (STAGED_N_VECTORS * n + V) * sizeof(Fr));
+    return rc;
+}
+
+// A batch into the staged set while the resident one proves (order: the head of this file): from [B][n_inputs] input values, solved, or
+// from [B][n_vars] values, converted and range-checked; wire columns, public inputs and the PI column gathered.  Everything on H, nothing
+// waits on the host unless a buffer has to grow, nothing of the resident batch is read or written.
+static int prover_stage(plonk_prover* p, const uint8_t* src_le32, size_t B, bool from_inputs) {
+    PLONK_REQUIRE(p && src_le32 && B, PLONK_ERR_ARG, "bad argument");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    StagedSlot& sl = p->staged;
+    PLONK_REQUIRE(p->wiring.n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    PLONK_REQUIRE(p->solver.n_inputs || !from_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
+    PLONK_REQUIRE(!sl.batch, PLONK_ERR_STATE, "stage: a batch of %zu is already staged (plonk_prover_advance takes it)", sl.batch);
+    PLONK_TRY(ctx_copy_stream(ctx));
+    hipStream_t h = ctx->copy_stream;
+    PLONK_TRY(staged_grow(p, B, from_inputs));
+    if (!sl.bad_input) PLONK_TRY(dev_alloc((void**)&sl.bad_input, sizeof(unsigned long long)));
+    if (!sl.ready) PLONK_CHECK_HIP(hipEventCreate(&sl.ready));
+    if (!sl.released) PLONK_CHECK_HIP(hipEventCreate(&sl.released));
+    const size_t V = p->wiring.n_vars, K = p->solver.n_inputs;
+    if (sl.released_pending) PLONK_CHECK_HIP(hipStreamWaitEvent(h, sl.released, 0));
+    sl.released_pending = false;  // H is in order: what it waited for once, every later stage is behind
+    const BatchSet bs = staged_set(p);
+    if (from_inputs) {
+        PLONK_CHECK_HIP(hipMemcpyAsync(bs.inputs, src_le32, B * K * sizeof(Fr), hipMemcpyHostToDevice, h));
+        PLONK_CHECK_HIP(hipMemsetAsync(bs.bad_input, 0xff, sizeof(unsigned long long), h));
+        enqueue_seed(p, bs, B, h);
+        enqueue_solve(p, bs, B, h);
+    } else {
+        PLONK_CHECK_HIP(hipMemcpyAsync(bs.vars, src_le32, B * V * sizeof(Fr), hipMemcpyHostToDevice, h));
+        PLONK_TRY(k_fr_to_mont_checked_on(h, bs.vars, B * V, bs.bad_input));
+    }
+    PLONK_TRY(enqueue_gather(p, bs, B, h));
+    PLONK_CHECK_HIP(hipEventRecord(sl.ready, h));
+    sl.bad_stride = from_inputs ? K : V;
+    sl.solved = from_inputs;
+    sl.batch = B;
+    return PLONK_OK;
+}
+
 extern "C" {
+
+int plonk_prover_stage_inputs(plonk_prover* p, const uint8_t* inputs_le32, size_t B) { return prover_stage(p, inputs_le32, B, true); }
+int plonk_prover_stage_variables(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_stage(p, vars_le32, B, false); }
+
+// the batch that is staged, 0: none
+int plonk_prover_staged(const plonk_prover* p, size_t* out_batch) {
+    PLONK_REQUIRE(p && out_batch, PLONK_ERR_ARG, "bad argument");
+    *out_batch = p->staged.batch;
+    return PLONK_OK;
+}
+
+// The staged batch becomes the resident one: C waits for the stage, the two sets change places by pointer, and what C has been given
+// so far — the outgoing batch's rounds and download, if the caller asked for them — is what the next stage will wait for.
+int plonk_prover_advance(plonk_prover* p, size_t* out_batch) {
+    PLONK_REQUIRE(p && out_batch, PLONK_ERR_ARG, "bad argument");
+    plonk_ctx* ctx = p->circuit.ctx;
+    PLONK_ENTER(ctx);
+    StagedSlot& sl = p->staged;
+    plonk_prover::Intake& in = p->intake;
+    PLONK_REQUIRE(sl.batch, PLONK_ERR_STATE, "advance: no batch is staged");
+    const size_t B = sl.batch;
+    PLONK_TRY(ensure_rounds(p, B));  // a staged batch larger than any before: the rounds' own buffers grow here, behind the outgoing batch
+    PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, sl.ready, 0));
+    std::swap(p->rounds.wit_lag, sl.wit_lag);
+    std::swap(in.pub, sl.pub);
+    std::swap(in.cap_b, sl.cap_b);
+    std::swap(in.vars, sl.vars);
+    std::swap(in.inputs, sl.inputs);
+    std::swap(in.bad_input, sl.bad_input);
+    std::swap(in.bad_stride, sl.bad_stride);
+    std::swap(p->solver.bad, sl.solve_bad);
+    in.vars_valid = true;
+    p->solver.valid = sl.solved;
+    in.resident_b = B;
+    sl.batch = 0;
+    PLONK_CHECK_HIP(hipEventRecord(sl.released, ctx->stream));
+    sl.released_pending = true;
+    *out_batch = B;
+    return PLONK_OK;
+}
 
 // witness columns [3][B][n] (A, B, C) and public inputs [B][n_public], canonical LE
 int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t B) {
@@ -181,7 +320,7 @@ int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const 
     if (p->intake.bad_input) PLONK_CHECK_HIP(hipMemsetAsync(p->intake.bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
     PLONK_TRY(plonk_fr_upload(ctx, p->rounds.wit_lag, abc_le32, 3 * B * p->circuit.n));
     if (p->circuit.n_public) PLONK_TRY(plonk_fr_upload(ctx, p->intake.pub, public_le32, B * p->circuit.n_public));
-    PLONK_TRY(fill_pi_column(p, B));
+    PLONK_TRY(fill_pi_column(p, p->rounds.wit_lag, p->intake.pub, B, ctx->stream));
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     p->intake.resident_b = B;
     p->intake.vars_valid = p->solver.valid = false;
@@ -194,6 +333,7 @@ int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const u
     PLONK_REQUIRE(p && cell_index && n_vars && (public_index || !p->circuit.n_public), PLONK_ERR_ARG, "bad argument");
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
+    PLONK_REQUIRE(!p->staged.batch, PLONK_ERR_STATE, "set_wiring: a batch of %zu is staged under the wiring in force", p->staged.batch);
     plonk_prover::Wiring& w = p->wiring;
     const size_t cells = 3 * p->circuit.n, l = p->circuit.n_public;
     for (size_t k = 0; k < cells; k++)
@@ -227,6 +367,7 @@ int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(p->wiring.n_vars && p->wiring.cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    PLONK_REQUIRE(!p->staged.batch, PLONK_ERR_STATE, "set_inputs: a batch of %zu is staged under the plan in force", p->staged.batch);
     plonk_prover::Solver& sv = p->solver;
     SolvePlan plan;
     PLONK_TRY(solve_plan_build(sv.gates_host, p->wiring.cell_host, p->circuit.n, p->wiring.n_vars, input_index, n_inputs, plan, out_missing_var));
@@ -234,8 +375,9 @@ int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // a batch in flight still walks the old plan
     sv.n_inputs = 0;
     p->intake.resident_b = 0;
-    dev_free_all({(void**)&sv.desc, (void**)&sv.order, (void**)&sv.level_start, (void**)&sv.input_index, (void**)&p->intake.inputs.buf, (void**)&sv.bad});
-    p->intake.inputs.cap = 0;
+    dev_free_all({(void**)&sv.desc, (void**)&sv.order, (void**)&sv.level_start, (void**)&sv.input_index, (void**)&p->intake.inputs.buf, (void**)&sv.bad,
+                  (void**)&p->staged.inputs.buf, (void**)&p->staged.solve_bad});  // (the staged set's: C has waited for the stage that used them)
+    p->intake.inputs.cap = p->staged.inputs.cap = 0;
     PLONK_TRY(dev_alloc((void**)&sv.desc, desc.size() * sizeof(uint32_t)));
     PLONK_TRY(dev_alloc((void**)&sv.order, plan.order.size() * sizeof(uint32_t)));
     PLONK_TRY(dev_alloc((void**)&sv.level_start, plan.level_start.size() * sizeof(uint32_t)));

@@ -5,10 +5,15 @@
       Poseidon circuit at B = 512, and for the chain at B = 1 at 2^11 and 2^16 (what a decision about a levelised form for small
       batches needs).
   (b) a step in bench.py's configuration — 20 contexts x 512 proofs, the same table budget, the 2^11 chain, every witness distinct —
-      with a fresh batch uploaded INSIDE the timed region, three ways in one process, alternating:
+      with a fresh batch uploaded INSIDE the timed region, five ways in one process, alternating:
         inputs    upload_input_values_async, 32 B per proof, the device solves
         values    upload_values_async of pre-packed [B][V] bytes (64 KiB per proof): the existing path, the baseline
         resident  the witnesses staged before the timed region: bench.py's own step
+        staged_inputs   the two-slot intake (csrc/prover_intake.h): batch k + 1 goes in by stage_input_values_async right after
+                        run(k) was enqueued — copy, solve and gathers on the copy stream beside batch k's rounds — then download(k),
+                        advance().  One stage per step, the first of a repeat with its advance inside the timed region too.
+        staged_values   the same with stage_values_async of the [B][V] bytes
+      -> profiles/intake_pipeline.json (--out), with the shader clock sampled over one more, untimed round of every way.
   (c) the host side it replaces: Program.fill_variable_assignments + BatchProver.upload per proof, on the same circuits.
 
 No ratio is fixed in advance: `inputs` is judged against the spread of `values` over its own repeats."""
@@ -71,7 +76,7 @@ def host_fill(pa, setup, program, inputs_of, count):
             "upload_ms_per_proof": round(1e3 * (t2 - t1) / count, 4), "total_ms_per_proof": round(1e3 * (t2 - t0) / count, 4)}
 
 
-def step_three_ways(pa, args):
+def step_ways(pa, args):
     """(b).  The [B][V] blobs of the baseline come from the device's own solve (plonk_prover_download_variables), which the test
     suite checks against the oracle: no Python loop over 10 240 x 2 048 values."""
     import contextlib
@@ -102,38 +107,79 @@ def step_three_ways(pa, args):
         small.append(a)
         full.append(f)
 
-    def step(mode):
+    def stage(mode):
+        for pr, a, f in zip(provers, small, full):
+            if mode == "staged_inputs":
+                pr.stage_input_values_async(a, B)
+            else:
+                pr.stage_values_async(f, B)
+
+    def step(mode, stage_next=False):
         for pr, a, f in zip(provers, small, full):
             if mode == "inputs":
                 pr.upload_input_values_async(a, B)
             elif mode == "values":
                 pr.upload_values_async(f, B)
             pr.run()
+            if stage_next:
+                (pr.stage_input_values_async(a, B) if mode == "staged_inputs" else pr.stage_values_async(f, B))
         raw = [pr.download_raw() for pr in provers]
         assert not any(any(st) for _, st in raw)
         return b"".join(r for r, _ in raw)
+
+    def steps(mode, count):
+        """`count` steps, every one with a fresh batch's bytes; the proofs of the last."""
+        out = None
+        if mode.startswith("staged_"):
+            stage(mode)
+        for i in range(count):
+            out = None  # (one step's records at a time, as a loop over step() holds them)
+            if mode.startswith("staged_"):
+                for pr in provers:
+                    pr.advance()
+            out = step(mode, stage_next=mode.startswith("staged_") and i + 1 < count)
+        return out
 
     def sync():
         for c in ctxs:
             c.sync()
 
     modes = tuple(args.modes.split(","))  # (a kernel trace of one way alone: --modes inputs)
-    proofs = {m: step(m) for m in modes for _ in range(max(1, args.warmup))}  # (the first step builds the MSM table)
-    assert len(set(proofs.values())) == 1, "the three ways must give the same proofs"
+    proofs = {m: steps(m, 2 if m.startswith("staged_") else 1) for m in modes for _ in range(max(1, args.warmup))}  # (the first step builds the MSM table)
+    assert len(set(proofs.values())) == 1, "every way must give the same proofs"
     ms = {m: [] for m in modes}
     for _ in range(args.repeats):
-        for m in modes:  # alternating: a drift of the clock falls on all three alike
+        for m in modes:  # alternating: a drift of the clock falls on all of them alike
             sync()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                step(m)
+            steps(m, args.steps)
             sync()
             ms[m].append(1e3 * (time.perf_counter() - t0) / args.steps)
+    # the shader clock under this load, from one more round of every way that is NOT timed: the sampler starts a process every
+    # ~0.2 s, which costs the timed steps 2-3 ms each when it runs beside them
+    from bench_legs import ClockSampler
+
+    sampler = ClockSampler(0)
+    sampler.start()
+    for m in modes:
+        steps(m, args.steps)
+    sync()
+    clocks = sampler.summary()
+    if clocks:
+        clocks["source"] = "rocm-smi --showclocks --showpower over one more, untimed round of every way, right behind the timed ones"
     knobs.close()
     out = {m: dict(spread(v), proofs_per_s=round(1e3 * B * S / statistics.median(v), 1)) for m, v in ms.items()}
     out["config"] = {"group_order": n, "batch": B, "contexts": S, "steps_per_repeat": args.steps, "lookup_budget_gb": args.lookup_budget_gb,
                      "bytes_per_proof": {"inputs": 32, "values": 32 * V}, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                      "table": setup.device_bases(ctxs[0]).lookup_info()}
+    out["clocks"] = clocks
+    for m in ("staged_inputs", "staged_values"):  # against the same session's `inputs` and `resident`, and the spread of the repeats
+        if m in out and "inputs" in out and "resident" in out:
+            lo, hi = out[m], out["inputs"]
+            out[m + "_vs_inputs"] = {"gain_ms": round(hi["median_ms"] - lo["median_ms"], 4),
+                                     "spread_ms": round(max(hi["max_ms"] - hi["min_ms"], lo["max_ms"] - lo["min_ms"]), 4),
+                                     "gain_exceeds_spread": lo["max_ms"] < hi["min_ms"],
+                                     "behind_resident_ms": round(lo["median_ms"] - out["resident"]["median_ms"], 4)}
     if "inputs" in out and "values" in out:
         v = out["values"]
         out["inputs_minus_values_ms"] = round(out["inputs"]["median_ms"] - v["median_ms"], 4)
@@ -155,7 +201,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5, help="(b): steps per timed repeat")
     ap.add_argument("--repeats", type=int, default=4, help="(b): timed repeats of each way, alternating")
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--modes", default="inputs,values,resident", help="(b): the ways to run, in their alternating order")
+    ap.add_argument("--modes", default="inputs,values,resident,staged_inputs,staged_values", help="(b): the ways to run, in their alternating order")
     ap.add_argument("--lookup-budget-gb", type=float, default=180.0, help="bench.py's DEFAULT_TABLE_GB")
     ap.add_argument("--large-log-n", type=int, default=16, help="(a): the large chain at B = 1 (0 = skip)")
     ap.add_argument("--bench-line", default="", help="a file holding bench.py's JSON line of the same session, to put beside (b)")
@@ -187,7 +233,7 @@ def main():
     if "c" in parts:
         result["c_host_fill"] = {"chain": host_fill(pa, setup, chain, chain_in, 64), "poseidon": host_fill(pa, setup, poseidon, poseidon_in, 64)}
     if "b" in parts:
-        result["b_step"] = step_three_ways(pa, args)
+        result["b_step"] = step_ways(pa, args)
     if args.bench_line and os.path.exists(args.bench_line):
         for line in open(args.bench_line):
             if line.startswith("{"):
