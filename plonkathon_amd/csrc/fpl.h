@@ -106,6 +106,28 @@ template <class P> PLONK_HD FpL<P> fpl_from_fp(const Fp<P>& a) {
     return r;
 }
 
+// s ? -a : a for a canonical a, the sign applied to the PACKED words: s = 0, or ~0 for the negative.  ~a read as a signed 256-bit
+// integer is -a - 1, so the eight words are XOR-ed with s, the top limb is taken by an arithmetic shift (it carries the sign of
+// the value, as in every normalised element) and the missing 1 goes to limb 0: 8 + 1 operations beside the unpack, against the 18
+// of fpl_cneg on the limbs.  Value in (-m, m).  Limbs 1..7 in [0, 2^29), limb 8 in [-2^23, 2^23), limb 0 in [0, 2^29]: 2^29
+// itself when s = ~0 and the low 29 bits of a are zero.  That is within the (-2^30, 2^30) fpl_mul allows ONE of its operands
+// (against a normalised one a column stays below 9 * 2^58 + 9 * 2^58 < 2^63, what fpl_dbg_check_product asserts), and fpl_norm
+// takes any int32; it is NOT an operand for fpl_sqr or fpl_mul_add, whose limbs must stay inside (-2^29, 2^29).
+template <class P> PLONK_HD FpL<P> fpl_from_fp_signed(const Fp<P>& a, uint32_t s) {
+    uint32_t v[8], u[9];
+#pragma unroll
+    for (int i = 0; i < 8; i++) v[i] = a.v[i] ^ s;
+    fp29_unpack(v, u);
+    FpL<P> r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = (int32_t)u[i];   // [0, 2^29)
+    r.l[0] -= (int32_t)s;                                  // + 1 for the negative: [0, 2^29]
+    r.l[8] = (int32_t)v[7] >> 8;                           // bits 232 .. 255, signed: [-2^23, 2^23)
+#pragma unroll
+    for (int i = 0; i < 9; i++) FPL_ANY_SIGN(r.l[i]);
+    return r;
+}
+
 // the same for a wave-uniform element (a kernel argument): the limbs stay in scalar registers
 template <class P> PLONK_HD FpL<P> fpl_from_fp_uniform(const Fp<P>& a) {
     uint32_t u[9];

@@ -200,9 +200,11 @@ PLONK_HD G1XyzzL g1l_from_xyzz(const G1Xyzz& p) {
 // (-6, 9); R = S2 - Y1 in (-3, 3); X3 = R^2 - PPP - 2Q in (-7, 5); D = Q - X3 in (-6, 9).  Products: P^2 <= 81,
 // X1 PP <= 14, P PP <= 18, R^2 <= 9, R D + Y1 PPP <= 27 + 4 — all below the 128 of fpl_mul.  Limbs: every
 // multiplicand is a normalised value or the difference of two, within (-2^29, 2^29).
-PLONK_HD bool g1l_madd_fast(G1XyzzL& p, const Fq& x2p, const Fq& y2p, bool neg_y = false) {
-    if (fp_is_zero(x2p) && fp_is_zero(y2p)) return false;
-    const FqL x2 = fpl_from_fp(x2p), y2 = fpl_cneg(fpl_from_fp(y2p), neg_y);   // y2 in (-m, m)
+//
+// g1l_madd_limbs is the addition itself on the unpacked addend: x2 normalised in [0, m); y2 in (-m, m) with limbs 1..8 as a
+// normalised value's or its negative's and limb 0 within [-2^29, 2^29] (fpl_from_fp_signed reaches 2^29: y2 only ever meets the
+// normalised ZZZ1 in fpl_mul, or fpl_norm).
+PLONK_HD bool g1l_madd_limbs(G1XyzzL& p, const FqL& x2, const FqL& y2) {
     if (p.inf) {
         p.x = x2;
         p.y = fpl_norm(y2);  // a negated y2 has limbs in (-2^29, 0]: the invariant wants them normalised (R = S2 - Y1 is squared)
@@ -227,6 +229,16 @@ PLONK_HD bool g1l_madd_fast(G1XyzzL& p, const Fq& x2p, const Fq& y2p, bool neg_y
     // Y3 = R (Q - X3) - Y1 PPP as one sum of products with a single reduction
     p.y = fpl_mul_add(rr, d, fpl_neg(p.y), ppp);
     return true;
+}
+PLONK_HD bool g1l_madd_fast(G1XyzzL& p, const Fq& x2p, const Fq& y2p, bool neg_y = false) {
+    if (fp_is_zero(x2p) && fp_is_zero(y2p)) return false;
+    return g1l_madd_limbs(p, fpl_from_fp(x2p), fpl_cneg(fpl_from_fp(y2p), neg_y));   // y2 in (-m, m)
+}
+// The comb loop's entry (msm_comb.h): the addend is known NOT to be the identity — the item's digit says so (MSM_COMB_SKIP) — so
+// there is no zero test, and false means "equal or opposite" alone.  sign: 0, or ~0 to add (x2, -y2); it is applied to the packed
+// words (fpl_from_fp_signed).
+PLONK_HD bool g1l_madd_signed(G1XyzzL& p, const Fq& x2p, const Fq& y2p, uint32_t sign) {
+    return g1l_madd_limbs(p, fpl_from_fp(x2p), fpl_from_fp_signed(y2p, sign));
 }
 
 // acc += q, both on lazy limbs (add-2008-s: 14 products under 13 reductions, ~2 700 instructions against ~4 600 for the

@@ -54,6 +54,12 @@
 #define MSM_COMB_REDO 0x80000000u
 PLONK_HD bool msm_comb_needs_redo(uint32_t v) { return (v & MSM_COMB_REDO) != 0 || v > MSM_DEFER_CAP; }
 
+// A digit of this value stands for an item whose table entry is the identity — an identity base, the all-zero code of a group of
+// the top tables, a group past the last scalar — and every kernel that reads digits passes it over without a load.  No real item
+// has it: a real scalar's digit is an index below 2^(h-1) <= 2^23 beside bit 31, and a virtual scalar's digit has bit 31 clear and
+// stays below (virtual (a - 1) + 1) << (h-1), which msm_comb_top_reach_ok keeps below 2^31 - ((a - 1) << (h-1)).
+#define MSM_COMB_SKIP 0xffffffffu
+
 PLONK_HD unsigned msm_comb_columns(unsigned h) { return (MSM_COMB_SCALAR_BITS + h - 1) / h; }
 
 // ---- combs with TOP TABLES (round 6) -----------------------------------------------------------
@@ -247,21 +253,38 @@ __global__ void __launch_bounds__(64) msm_comb_top_fill_kernel(const G1Affine* t
     }
 }
 
+// skip[i] = 1 where base i is the identity (MsmLookupTable::base_skip): every entry of its block is the identity.  No other entry of
+// a base's block is: E_P[idx] = c R^-1 P with c odd and |c| < 2^(a (h-1) + 1) < r.
+__global__ void msm_comb_base_skip_kernel(const G1Affine* bases, size_t n, uint8_t* skip) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        G1Affine b;
+        b.x = fp_load(&bases[i].x);
+        b.y = fp_load(&bases[i].y);
+        skip[i] = g1_affine_is_identity(b) ? 1 : 0;
+    }
+}
+
 // digits[(m * A + j) * nd + i] = column j of scalar i of MSM m: the index of its table entry in bits 0 .. H-2, bit 31 set when the
 // entry is to be subtracted.  Scalar vector of MSM m: msm_scalar_row.  nd = n without top
 // tables.  TOP (see msm_comb_shape): a workgroup takes PER = g floor(256 / g) scalars — whole groups — and, after the columns,
 // lane t < PER / g folds the top codes of its group into the digit of virtual scalar n + grp / A of column grp % A
 // (nd = n + ceil(ceil(n / g) / A); a group past the last scalar gets the all-zero code: the identity entry of its block).
+// Items whose entry is the identity get MSM_COMB_SKIP: every column of an identity base (base_skip), and a group whose codes are all
+// zero — an identity base's code counts as zero, its share of every joint entry being the identity.  The kernel also zeroes
+// n_deferred[m]: it runs before the kernels that count.
 template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_digits_kernel(const Fr* scalars, size_t n, size_t stride, size_t inner,
-                                                                                              size_t outer_stride, size_t m0, uint32_t* digits, size_t nd) {
+                                                                                              size_t outer_stride, size_t m0, uint32_t* digits, size_t nd,
+                                                                                              const uint8_t* base_skip, uint32_t* n_deferred) {
     constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
     constexpr unsigned A = SH.a, L = A * H;
     static_assert(L <= 9 * 32 && H <= MSM_COMB_MAX_TEETH, "the recoded scalar is kept in nine words");
     constexpr unsigned PER = TOP ? (256 / (SH.top_g ? SH.top_g : 1)) * (SH.top_g ? SH.top_g : 1) : 256;
     const size_t m = m0 + blockIdx.y, i = (size_t)blockIdx.x * PER + threadIdx.x;  // (a grid row per MSM: no division per lane)
     const bool live = threadIdx.x < PER && i < n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) n_deferred[m] = 0;
     int code = 0;
     if (live) {
+        const bool skip = base_skip[i] != 0;
         const Fr* sc = msm_scalar_row(scalars, m, stride, inner, outer_stride);
         const Fr s = fp_load(sc + i);  // the Montgomery residue s R mod r, taken as the integer it is: the table holds multiples of R^-1 P
         // odd representative: s, or r - s with the sign of the base flipped (r is odd; s = 0 becomes r, and r P = O comes out of the sums)
@@ -284,6 +307,7 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
             if constexpr (sh + SH.top_bits > 32 && hi + 1 < 8) u |= sp[hi + 1] << (32 - sh);
             code = (int)(u & ((1u << SH.top_bits) - 1u));
             if (even) code = -code;
+            if (skip) code = 0;
 #pragma unroll
             for (unsigned k = 0; k < 9; k++) {  // v >> 1 keeps bits 0 .. L-2
                 if (k > ((L - 1) >> 5)) w[k] = 0;
@@ -292,18 +316,53 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
         }
         w[(L - 1) >> 5] |= 1u << ((L - 1) & 31);
         uint32_t* out = digits + (m * A) * nd + i;
-#pragma unroll
-        for (unsigned j = 0; j < A; j++) {
-            uint32_t idx = 0;
-#pragma unroll
-            for (unsigned k = 0; k < H; k++) {
-                const unsigned p = j + A * k;
-                idx |= ((w[p >> 5] >> (p & 31)) & 1u) << k;
-            }
+        // Column j's index is the bits j + A k of t.  Shifted right by (A - 1) k + c0, tooth k's bits of the C columns from c0 on sit at
+        // k + (j - c0): one shift per tooth and chunk of columns, and the teeth k, k + C, .. land in disjoint windows [k, k + C) that
+        // are merged before the columns take their bits — diag[j - c0] = idx_j << (j - c0), from one AND-OR per column and C teeth.
+        // C: as many columns as keep the H + C - 1 bits of a diagonal inside a word.  (Below six teeth a column has too few bits for
+        // the shared shifts to pay: those combs gather bit by bit.)
+        const auto emit = [&](unsigned j, uint32_t idx) PLONK_LAMBDA_INLINE {
             const uint32_t top = idx >> (H - 1), mask = (1u << (H - 1)) - 1u;
             const uint32_t low = top ? (idx & mask) : (~idx & mask);  // top tooth -1: minus the entry of the complemented teeth
             const uint32_t neg = (top ? 0u : 1u) ^ (even ? 1u : 0u);
             out[(size_t)j * nd] = low | (neg << 31);
+        };
+        if constexpr (H < 6) {
+#pragma unroll
+            for (unsigned j = 0; j < A; j++) {
+                uint32_t idx = 0;
+#pragma unroll
+                for (unsigned k = 0; k < H; k++) {
+                    const unsigned p = j + A * k;
+                    idx |= ((w[p >> 5] >> (p & 31)) & 1u) << k;
+                }
+                emit(j, idx);
+            }
+        } else {
+            constexpr unsigned C = A < 33 - H ? A : 33 - H;
+#pragma unroll
+            for (unsigned c0 = 0; c0 < A; c0 += C) {
+                uint32_t diag[C] = {};
+#pragma unroll
+                for (unsigned k0 = 0; k0 < C && k0 < H; k0++) {
+                    uint32_t v = 0, teeth = 0;
+#pragma unroll
+                    for (unsigned k = k0; k < H; k += C) {
+                        const unsigned s = (A - 1) * k + c0, q = s >> 5, sh = s & 31;
+                        const uint32_t win = sh ? (w[q] >> sh) | (q + 1 < 9 ? w[q + 1] << (32 - sh) : 0u) : w[q];
+                        v |= win & (((1u << C) - 1u) << k);
+                        teeth |= 1u << k;
+                    }
+#pragma unroll
+                    for (unsigned j = 0; j < C; j++) diag[j] |= v & (teeth << j);
+                }
+#pragma unroll
+                for (unsigned j = c0; j < c0 + C && j < A; j++) emit(j, diag[j - c0] >> (j - c0));
+            }
+        }
+        if (skip) {  // (written over afterwards, by the lanes concerned alone: nothing per column for the others)
+#pragma unroll 1
+            for (unsigned j = 0; j < A; j++) out[(size_t)j * nd] = MSM_COMB_SKIP;
         }
     }
     if constexpr (TOP) {
@@ -320,7 +379,7 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
                 pw *= B;
             }
             const size_t v = grp / A, j = grp - v * A;
-            digits[(m * A + j) * nd + n + v] = (uint32_t)((v * (A - 1) + j) << (H - 1)) + idx;
+            digits[(m * A + j) * nd + n + v] = idx == (SH.top_entries - 1) / 2 ? MSM_COMB_SKIP : (uint32_t)((v * (A - 1) + j) << (H - 1)) + idx;  // (B^g - 1) / 2: every code zero
         }
     }
 }
@@ -355,6 +414,9 @@ PLONK_HD uint32_t msm_comb_slot(const MsmCombPlan& pl, uint32_t a, uint32_t j, u
     return r < pl.q ? j * pl.q + r : a * pl.q + ulo + j + (r - pl.q);
 }
 
+// NARROW: the table has at most 2^32 entries (decided per launch on the host), so an entry's index is formed in one 32-bit register
+// and scaled once; the wide form is for larger tables.
+template <bool NARROW>
 __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_kernel(const G1Affine* lookup, unsigned hb, unsigned a,
                                                                              const uint32_t* digits, size_t n, unsigned G,
                                                                              G1Xyzz* partial, MsmDeferred* deferred, size_t deferred_stride,
@@ -388,13 +450,24 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_kernel(cons
     }
     G1XyzzL run = g1l_identity();
     auto flush = [&]() { red[slot] = g1l_to_piece(run); };  // [0, 4m) words: what g1l_from_piece takes
+    const uint32_t* col = dg + (size_t)j * n;  // the digits of the lane's column
     for (uint32_t k = 0; k < count; k++) {
-        const uint32_t d = dg[(size_t)j * n + i];
-        const G1Affine* src = tab + (((size_t)(i + (i >= nr_rel ? top_delta : 0u)) << hb) + (d & 0x7fffffffu));
-        const Fq x = fp_load(&src->x), y = fp_load(&src->y);
-        if (!g1l_madd_fast(run, x, y, (d >> 31) != 0) && !(fp_is_zero(x) && fp_is_zero(y))) {  // see msm_accumulate_kernel
-            const uint32_t sl = atomicAdd(n_deferred + m, 1u);
-            if (sl < MSM_DEFER_CAP) deferred[(size_t)m * deferred_stride + sl] = MsmDeferred{(uint32_t)(j * n + s0 + i), d};
+        const uint32_t d = col[i];
+        if (d != MSM_COMB_SKIP) {  // (an identity entry is known by its digit: no test of the entry itself)
+            const bool is_virtual = i >= nr_rel;
+            const uint32_t blk = i + (is_virtual ? top_delta : 0u), e = d & 0x7fffffffu;
+            const G1Affine* src;
+            if constexpr (NARROW) src = tab + ((blk << hb) + e);
+            else src = tab + (((size_t)blk << hb) + e);
+            const Fq x = fp_load(&src->x), y = fp_load(&src->y);
+            // a JOINT entry can still be the identity under non-zero codes when the group's bases are related (a duplicated base with
+            // opposite codes): the virtual scalars, one item in a g + 1, keep the test of the entry
+            bool add = true;
+            if (is_virtual) add = !(fp_is_zero(x) && fp_is_zero(y));
+            if (add && !g1l_madd_signed(run, x, y, (uint32_t)((int32_t)d >> 31))) {  // equal or opposite: see msm_accumulate_kernel
+                const uint32_t sl = atomicAdd(n_deferred + m, 1u);
+                if (sl < MSM_DEFER_CAP) deferred[(size_t)m * deferred_stride + sl] = MsmDeferred{(uint32_t)(j * n + s0 + i), d};
+            }
         }
         i += step;
         if (i >= nsub && k + 1 < count) {  // a left-over lane moves on to the next column
@@ -402,6 +475,7 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_kernel(cons
             run = g1l_identity();
             slot++;
             j++;
+            col += n;
             i = pl.n_main;
         }
     }
@@ -475,7 +549,7 @@ template <unsigned LPM> __global__ void __launch_bounds__(64) msm_comb_finalize_
 #pragma unroll 1
             for (uint32_t k = 0; k < nd; k++) {
                 const MsmDeferred e = deferred[m * deferred_stride + k];  // `bucket` carries the item j * n + i here
-                if (e.bucket / n != (uint32_t)j) continue;
+                if (e.bucket / n != (uint32_t)j || e.entry == MSM_COMB_SKIP) continue;  // (the comb kernel defers no skipped item)
                 const size_t i = e.bucket - (size_t)j * n;
                 const G1Affine* src = lookup + ((msm_comb_block_of(i, n_real, top_delta) << hb) + (e.entry & 0x7fffffffu));
                 // deferred for being exceptional against its LANE's sum at the time; against the column's sum it normally is not
@@ -511,6 +585,7 @@ __global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* look
 #pragma unroll 1
         for (size_t i = tid; i < n; i += 256) {
             const uint32_t d = dg[(size_t)j * n + i];
+            if (d == MSM_COMB_SKIP) continue;
             const G1Affine* src = lookup + ((msm_comb_block_of(i, n_real, top_delta) << hb) + (d & 0x7fffffffu));
             G1Affine pt;
             pt.x = fp_load(&src->x);
@@ -604,7 +679,7 @@ static bool msm_comb_well_formed(const MsmLookupTable* t) {
     const bool top = t->top_g != 0;
     if (top && !msm_comb_top_ok(t->bits)) return false;
     const MsmCombShape sh = msm_comb_shape(t->bits, top);
-    return t->windows == sh.a && t->top_bits == sh.top_bits && t->top_g == sh.top_g &&
+    return t->base_skip && t->windows == sh.a && t->top_bits == sh.top_bits && t->top_g == sh.top_g &&
            t->bytes == (msm_comb_blocks(t->n_points, sh) << (t->bits - 1)) * sizeof(G1Affine);
 }
 
@@ -632,9 +707,9 @@ static int msm_comb_build(plonk_ctx* ctx, const plonk_srs* srs, unsigned h, bool
     const unsigned a = sh.a, sb = h - 1 < MSM_COMB_SEG_BITS ? h - 1 : MSM_COMB_SEG_BITS;
     const size_t n = srs->n_points, half = (size_t)1 << (h - 1), stage = msm_comb_stage_entries(n, h), chunk_bases = stage / half;
     const size_t blocks = msm_comb_blocks(n, sh);
-    void *gx = nullptr, *gb = nullptr, *dx = nullptr, *db = nullptr, *tmp = nullptr, *tab = nullptr, *pb = nullptr;
+    void *gx = nullptr, *gb = nullptr, *dx = nullptr, *db = nullptr, *tmp = nullptr, *tab = nullptr, *pb = nullptr, *skip = nullptr;
     auto fail = [&]() {
-        for (void* q : {gx, gb, dx, db, tmp, tab, pb})
+        for (void* q : {gx, gb, dx, db, tmp, tab, pb, skip})
             if (q) hipFree(q);
         (void)hipGetLastError();
         plonk_set_error("the %u-tooth comb table (%zu MiB) does not fit in device memory", h, msm_comb_bytes(n, h, top) >> 20);
@@ -647,6 +722,8 @@ static int msm_comb_build(plonk_ctx* ctx, const plonk_srs* srs, unsigned h, bool
     if (!plonk_dev_malloc(&dx, n * (sb ? sb : 1) * sizeof(G1Xyzz))) return fail();
     if (!plonk_dev_malloc(&db, n * (sb ? sb : 1) * sizeof(G1Affine))) return fail();
     if (!plonk_dev_malloc(&pb, n * sizeof(G1Affine))) return fail();
+    if (!plonk_dev_malloc(&skip, n)) return fail();
+    PLONK_LAUNCH(msm_comb_base_skip_kernel, grid1(n), dim3(256), 0, ctx->stream, (const G1Affine*)srs->bases, n, (uint8_t*)skip);
     // P'_i = R^-1 P_i (the scalars arrive as Montgomery residues), through the staging buffers of the next step
     PLONK_LAUNCH(msm_comb_scale_kernel, grid1(n, 64, 2048), dim3(64), 0, ctx->stream, (const G1Affine*)srs->bases, n, msm_comb_scale_constant(), (G1Xyzz*)gx);
     g1_batch_to_affine(ctx, (const G1Xyzz*)gx, (G1Affine*)pb, n);
@@ -687,6 +764,7 @@ static int msm_comb_build(plonk_ctx* ctx, const plonk_srs* srs, unsigned h, bool
     t->top_bits = sh.top_bits;
     t->top_g = sh.top_g;
     t->data = (G1Affine*)tab;
+    t->base_skip = (uint8_t*)skip;
     t->bytes = blocks * half * sizeof(G1Affine);
     return PLONK_OK;
 }
@@ -706,7 +784,8 @@ static void msm_comb_verify(plonk_ctx* ctx, const plonk_srs* srs, const MsmLooku
 // digits kernel of the comb with h teeth (one instantiation per tooth count: the bit gather is unrolled at compile time); TOP: the
 // comb with top tables, whose workgroups take whole groups of scalars and add the virtual scalars' digits (nd = n + their number)
 template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ctx, const Fr* d_scalars, size_t n, size_t stride, size_t inner,
-                                                                   size_t outer_stride, size_t M, uint32_t* digits, size_t nd) {
+                                                                   size_t outer_stride, size_t M, uint32_t* digits, size_t nd, const uint8_t* base_skip,
+                                                                   uint32_t* n_deferred) {
     if constexpr (!TOP || msm_comb_top_ok(H)) {
         constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
         constexpr unsigned G = TOP ? SH.top_g : 1, PER = (256 / G) * G;
@@ -715,15 +794,15 @@ template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ct
             const size_t gv = ((nd - n) * SH.a + PER / G - 1) / (PER / G);
             gx = gx > gv ? gx : gv;
         }
-        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
+        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, const uint8_t*, uint32_t*) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
         for (size_t m0 = 0; m0 < M; m0 += 32768) {  // (a grid's second dimension ends at 65 535)
             const size_t rows = M - m0 < 32768 ? M - m0 : 32768;
             PLONK_LAUNCH(kern, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, ctx->stream, d_scalars, n, stride, inner,
-                         outer_stride, m0, digits, nd);
+                         outer_stride, m0, digits, nd, base_skip, n_deferred);
         }
     }
 }
-typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t);
+typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, const uint8_t*, uint32_t*);
 template <bool TOP, unsigned... H> static msm_comb_digits_fn msm_comb_digits_for(unsigned h, std::integer_sequence<unsigned, H...>) {
     msm_comb_digits_fn fn = nullptr;
     ((h == H + 2 && (!TOP || msm_comb_top_ok(H + 2)) ? (void)(fn = &msm_comb_launch_digits<H + 2, TOP>) : (void)0), ...);
@@ -754,14 +833,15 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     const auto teeth = std::make_integer_sequence<unsigned, MSM_COMB_MAX_TEETH - 1>();
     const msm_comb_digits_fn digits_fn = top ? msm_comb_digits_for<true>(h, teeth) : msm_comb_digits_for<false>(h, teeth);
     PLONK_REQUIRE(digits_fn, PLONK_ERR_ARG, "no comb of %u teeth", h);
-    PLONK_CHECK_HIP(hipMemsetAsync(n_deferred, 0, M * 4, ctx->stream));
     PLONK_TRY(prof_begin(ctx, "msm_digits", (double)M * (double)n * (32.0 + 4.0 * a)));
-    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n);
+    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n, srs->shared->base_skip, n_deferred);  // (also zeroes n_deferred)
     PLONK_TRY(prof_end(ctx));
     const size_t lds = (size_t)(MSM_BLOCK + a) * sizeof(G1Xyzz);
     PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));
-    PLONK_LAUNCH(msm_comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a, (const uint32_t*)digits, n, G, partial,
-                 deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
+    const bool narrow = srs->shared->bytes / sizeof(G1Affine) <= ((uint64_t)1 << 32);  // every entry index fits 32 bits
+    const auto comb_kernel = narrow ? msm_comb_kernel<true> : msm_comb_kernel<false>;
+    PLONK_LAUNCH(comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a,
+                 (const uint32_t*)digits, n, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
     PLONK_TRY(prof_end(ctx));
     const G1Xyzz* sums = partial;
     unsigned Gf = G;

@@ -22,6 +22,7 @@ static void lut_attach(plonk_srs* srs, MsmLookupTable* t) {  // g_lut_mu held
         for (size_t k = 0; k < g_luts.size(); k++)
             if (g_luts[k] == srs->shared) g_luts.erase(g_luts.begin() + k);
         hipFree(srs->shared->data);
+        hipFree(srs->shared->base_skip);
         delete srs->shared;
     }
     srs->shared = t;

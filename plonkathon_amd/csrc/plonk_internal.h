@@ -128,6 +128,7 @@ struct MsmLookupTable {
     unsigned top_bits = 0, top_g = 0;  // comb with top tables (msm_comb.h: windows = floor(254 / bits)): R and the bases per group; 0, 0 = none
     G1Affine* data = nullptr;  // comb: data[(i << (h - 1)) + idx]; windows: data[((w * n_points + i) << (c - 1)) + d - 1]
     size_t bytes = 0;
+    uint8_t* base_skip = nullptr;  // comb: base_skip[i] = 1 where base i is the identity — every entry of its block is, and its items are skipped (n_points bytes, device)
     double build_s = 0;      // wall time of the build (reported by bench.py)
     int refs = 0;
 };

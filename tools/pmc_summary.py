@@ -25,7 +25,8 @@ def rows(tag):
         return []
     rs = list(csv.DictReader(open(paths[0])))
     rs.sort(key=lambda r: int(r.get("Dispatch_Id", 0)))
-    return [(r["Kernel_Name"].split("(")[0].replace("void ", ""), int(r["Grid_Size"]), float(r["Counter_Value"])) for r in rs]
+    name = lambda r: r["Kernel_Name"].split("(")[0].replace("void ", "").replace("msm_comb_kernel<true>", "msm_comb_kernel").replace("msm_comb_kernel<false>", "msm_comb_kernel")
+    return [(name(r), int(r["Grid_Size"]), float(r["Counter_Value"])) for r in rs]
 
 
 res = {"units": "bytes; HBM traffic = factor * FETCH_SIZE * 1024 + WRITE_SIZE * 1024 (tools/pmc_summary.py)", "factors": {}, "ntt": {}, "bench": {}, "kernels": []}

@@ -30,7 +30,9 @@ def launches(tag):
     per = collections.OrderedDict()
     for p in paths:
         for r in csv.DictReader(open(p)):
-            key = (int(r["Dispatch_Id"]), r["Kernel_Name"].split("(")[0].replace("void ", ""), int(r["Grid_Size"]), int(r["Workgroup_Size"]))
+            name = r["Kernel_Name"].split("(")[0].replace("void ", "")
+            name = "msm_comb_kernel" if name.startswith("msm_comb_kernel<") else name  # (one instance per entry-index width)
+            key = (int(r["Dispatch_Id"]), name, int(r["Grid_Size"]), int(r["Workgroup_Size"]))
             d = per.setdefault(key, {"dur_ns": float(r["End_Timestamp"]) - float(r["Start_Timestamp"])})
             d[r["Counter_Name"]] = d.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
     by = collections.OrderedDict()
