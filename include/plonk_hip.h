@@ -200,7 +200,10 @@ int plonk_g1_msm(plonk_ctx* ctx, plonk_srs* srs, const void* d_scalars, size_t n
  * PLONK_MSM_TABLE_GB gigabytes if that variable is set: the big tables are a memory-for-time trade the caller opts into
  * explicitly.  Bucket method when nothing fits or for plonk_srs_load_affine bases; mode 1: never; mode 2: use `bits`
  * (h, or c with | 16) for every base set (tests).  The automatic choice weighs combs with and without top tables alike; an
- * explicit `bits` means the plain comb of h teeth, and mode | 32 the one with top tables (PLONK_ERR_ARG if h takes none). */
+ * explicit `bits` means the plain comb of h teeth, and mode | 32 the one with top tables (PLONK_ERR_ARG if h takes none).
+ * mode | 64 (a TEST flag; only with mode 2 and a comb, PLONK_ERR_ARG with mode 0, mode 1 or | 16): the comb's accumulation kernel
+ * runs in its 64-bit entry-index form whatever the table's size — the form that tables of more than 2^32 entries (275 GB) select
+ * by themselves — so that it is reachable at toy sizes.  The table is the same one: the flag is no part of its identity. */
 int plonk_msm_lookup_configure(plonk_ctx* ctx, int mode, unsigned bits, size_t budget_bytes);
 /* bits (teeth h / window bits c) of the table currently attached to `srs` (0 = none: its MSMs use the bucket method) */
 int plonk_srs_lookup_bits(const plonk_srs* srs, unsigned* out_bits);

@@ -838,7 +838,8 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     PLONK_TRY(prof_end(ctx));
     const size_t lds = (size_t)(MSM_BLOCK + a) * sizeof(G1Xyzz);
     PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));
-    const bool narrow = srs->shared->bytes / sizeof(G1Affine) <= ((uint64_t)1 << 32);  // every entry index fits 32 bits
+    // every entry index fits 32 bits (and no test asked for the wide form: plonk_msm_lookup_configure mode | 64)
+    const bool narrow = !ctx->msm_comb_wide && srs->shared->bytes / sizeof(G1Affine) <= ((uint64_t)1 << 32);
     const auto comb_kernel = narrow ? msm_comb_kernel<true> : msm_comb_kernel<false>;
     PLONK_LAUNCH(comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a,
                  (const uint32_t*)digits, n, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
