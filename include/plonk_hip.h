@@ -265,7 +265,28 @@ int plonk_prover_destroy(plonk_prover* p);
 #define PLONK_PROVER_SOLVE_FORM_MASK (3u << 16)
 #define PLONK_PROVER_SOLVE_LANES 1u
 #define PLONK_PROVER_SOLVE_LEVELS 2u
+/* PLONK_PROVER_BLINDING: zero-knowledge proofs.  Every committed polynomial gets the PLONK paper's blinding (section 8.3, b1..b11:
+ * a, b, c gain (b X + b') Z_H, z gains a quadratic multiple of Z_H, the three parts of the quotient are re-split with two more), so
+ * that the nine commitments and the six evaluations say nothing about the witness and two proofs of one witness differ.  The
+ * unchanged verifier accepts them.  The quotient is then interpolated from four cosets instead of three, and the commitments add
+ * multiples of [tau^(n+k)] - [tau^k], k < 6: PLONK_ERR_ARG, the numbers in plonk_last_error(), for a group order below 8, for an
+ * SRS of fewer than n + 6 powers and for one that holds no monomial powers.  Combines with every other option; switching it drops
+ * the resident batch (a staged one stays).  With the option set, plonk_prover_run needs blinders from one of two sources,
+ * PLONK_ERR_STATE without:
+ *   plonk_prover_set_blinders   explicit values [batch][11] canonical LE (b[0..10]: a's two, b's, c's, z's three, the two of the
+ *                               quotient split), PLONK_ERR_ARG for one that is not below r.  They serve the NEXT run, which must be of
+ *                               `batch` proofs (PLONK_ERR_STATE otherwise); tests, and callers with a generator of their own.
+ *   plonk_prover_seed_blinders  the device derives them: per proof a Merlin transcript "plonk-blinding" absorbs "seed" (the 32 bytes),
+ *                               "run" (the number of blinded runs since this call, 8 bytes LE) and "index" (the proof's index in the
+ *                               batch, 8 bytes LE), and b[k] is its k-th challenge "b" of 255 bytes read big-endian mod r.  One seed
+ *                               never blinds two runs alike.
+ * The blinders belong to a run, not to an intake slot: staging and plonk_prover_advance are as before.
+ * THE SEED IS A SECRET.  Whoever can predict or learn it can recompute every blinder and strip the blinding: the proofs are then
+ * as revealing as unblinded ones.  Take it from the operating system's generator, keep it out of logs, never reuse it across provers. */
+#define PLONK_PROVER_BLINDING (1u << 20)
 int plonk_prover_set_options(plonk_prover* p, unsigned flags);
+int plonk_prover_set_blinders(plonk_prover* p, const uint8_t* blinders_le32, size_t batch);
+int plonk_prover_seed_blinders(plonk_prover* p, const uint8_t seed[32]);
 int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const uint8_t* public_le32, size_t batch);
 /* The same inputs at n_vars * 32 bytes per proof instead of 3 * n * 32: the wiring is given once per circuit —
  * cell_index[3][n] = index of the variable each wire cell (column L / R / O, row) carries, n_vars for an empty cell

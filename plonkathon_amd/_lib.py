@@ -78,6 +78,8 @@ SIGNATURES = {
     "plonk_msm_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint]),
     "plonk_prover_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, _u8p, ctypes.c_size_t, c_void_pp]),
     "plonk_prover_set_options": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint]),
+    "plonk_prover_set_blinders": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
+    "plonk_prover_seed_blinders": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "plonk_prover_plan_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint)]),
     "plonk_prover_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "plonk_prover_upload_witness": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t]),

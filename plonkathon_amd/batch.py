@@ -6,6 +6,7 @@ the same `Proof` objects.  All five rounds and the Fiat-Shamir transcript run on
 (plonk_prover_* in include/plonk_hip.h), with one host synchronisation per batch.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -38,7 +39,9 @@ except ImportError:  # pragma: no cover - pure-Python equivalent of the packer (
 class BatchProver:
     SOLVE_FORMS = {None: 0, "lanes": 1, "levels": 2}  # PLONK_PROVER_SOLVE_FORM
 
-    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False, segments=None, solve=None):
+    BLINDING = 1 << 20  # PLONK_PROVER_BLINDING
+
+    def __init__(self, setup: Setup, program: Program, ctx=None, lagrange_commits=False, segments=None, solve=None, blinding=False):
         """`ctx`: the Context (HIP stream) to run on; several BatchProvers on distinct contexts of one
         GPU overlap each other's latency-bound kernels (transcript, inversions) with MSM work.
         `lagrange_commits`: commit a_1, b_1, c_1, z_1 from Lagrange values over the Lagrange-basis SRS
@@ -46,7 +49,14 @@ class BatchProver:
         `segments`: None = automatic (`segments_for`); a power of two S forces the per-proof scans of rounds 2, 4 and 5 to run
         cut into S segments per proof (PLONK_PROVER_SEGMENTS_LOG2; 1 = one workgroup per proof): tests and A/B runs, same proofs.
         `solve`: None = automatic (`solve_plan`); "lanes" / "levels" force the witness solver of `upload_inputs*` to run one lane
-        per proof / one workgroup per proof over dependency levels (PLONK_PROVER_SOLVE_FORM): tests and A/B runs, same values."""
+        per proof / one workgroup per proof over dependency levels (PLONK_PROVER_SOLVE_FORM): tests and A/B runs, same values.
+        `blinding`: False = the reference's proofs, which are a deterministic function of the witness.  True or a 32-byte seed =
+        zero-knowledge proofs (PLONK_PROVER_BLINDING: the PLONK paper's blinders; needs group_order >= 8 and an SRS of
+        group_order + 6 powers); the same verifier accepts them.  True seeds the device's generator from os.urandom once per
+        prover; a seed given here must be as secret and as unpredictable: whoever knows it can strip the blinding.
+        `set_blinders` gives the next run explicit values instead."""
+        if not isinstance(blinding, (bool, bytes, bytearray)) or (not isinstance(blinding, bool) and len(blinding) != 32):
+            raise ValueError("blinding must be False, True or a 32-byte seed")
         if solve not in self.SOLVE_FORMS:
             raise ValueError('solve must be None, "lanes" or "levels"')
         self.group_order = program.group_order
@@ -75,8 +85,13 @@ class BatchProver:
                 raise ValueError("segments must be a power of two")
             flags |= min(segments.bit_length(), 15) << 8  # k + 1 in bits 8-11; the library checks the range
         flags |= self.SOLVE_FORMS[solve] << 16
+        self.blinding = blinding is not False
+        if self.blinding:
+            flags |= self.BLINDING
         if flags:
             check(self.ctx.L.plonk_prover_set_options(self._h, flags))
+        if self.blinding:
+            check(self.ctx.L.plonk_prover_seed_blinders(self._h, os.urandom(32) if blinding is True else bytes(blinding)))
         # the wiring goes to the device once; a batch is then only the variables' values (V x 32 B per proof)
         self._getter = None
         if self._vars:
@@ -305,6 +320,17 @@ class BatchProver:
         self._resident = B
 
     # ---- proving --------------------------------------------------------------------------------
+    def set_blinders(self, blinders):
+        """Explicit blinders for the NEXT run instead of the seed's: a list of proofs, each a list of eleven integers below r (b[0..10]
+        of csrc/prover_blind.h), or the same as [B][11] 32-byte little-endian values.  The run must be of that many proofs."""
+        if not isinstance(blinders, (bytes, bytearray)):
+            if any(len(row) != 11 for row in blinders):
+                raise ValueError("set_blinders: eleven blinders per proof")
+            blinders = b"".join(int(v).to_bytes(32, "little") for row in blinders for v in row)
+        if not blinders or len(blinders) % (11 * 32):
+            raise ValueError("set_blinders: expected a multiple of %d bytes" % (11 * 32))
+        check(self.ctx.L.plonk_prover_set_blinders(self._h, bytes(blinders), len(blinders) // (11 * 32)))
+
     def run(self, B=None):
         """Enqueue the five rounds for the resident witnesses (asynchronous)."""
         B = self._resident if B is None else B

@@ -43,6 +43,7 @@ constexpr size_t proof_bytes(bool compressed) { return compressed ? PROOF_BYTES_
 enum { FX_QM = 0, FX_QL, FX_QR, FX_QO, FX_QC, FX_S1, FX_S2, FX_S3, FX_COUNT };
 #define PROVER_MAX_LOG_N 16  // the largest group order the lock-step prover accepts: what the suite checks (tests/test_gpu_prover_large.py)
 #define QCOSETS 3  // cosets of size n the lock-step prover evaluates the quotient on (deg t < 3n)
+#define QCOSETS_BLINDED 4  // under PLONK_PROVER_BLINDING (prover_blind.h): deg t = 3n + 5
 
 // A device buffer that an upload fills on the copy stream while the previous batch may still be reading it.
 struct Staging {
@@ -80,7 +81,9 @@ struct plonk_prover {
         Fr g;                // fixed coset offset (Montgomery)
         Fr w, n_inv, half;   // the n-th root of unity, 1 / n, 1 / 2
         // The quotient has degree < 3n, so THREE cosets of the n-th roots of unity determine it: x = g mu^r w^j, r < 3 (mu = the
-        // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.
+        // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.  A blinded
+        // prover (prover_blind.h) takes all four: qcosets = 4, and plonk_prover_set_options rebuilds the coset forms as [4][n].
+        unsigned qcosets;    // QCOSETS or QCOSETS_BLINDED
         Fr* fixed_lag;       // [8][n]   Lagrange values
         Fr* fixed_coef;      // [8][n]   coefficient forms
         Fr* fixed_big;       // [8][3][n]  the circuit polynomials on the three cosets
@@ -89,7 +92,7 @@ struct plonk_prover {
         Fr* g_pow;           // [3][n]   (g mu^r)^i: the load-side scaling of the size-n transform that evaluates on coset r
         Fr* ginv_pow;        // [3][n]   (g mu^r)^-i / 2n: the store-side scaling of the inverse transform of coset r (its 1/n folded in)
         const Fr* roots;     // [n]      w^i (owned by ctx)
-        Fr zh_inv[QCOSETS];  // 1 / (g^n * i^r - 1): Z_H is constant on a coset
+        Fr zh[4], zh_inv[4]; // g^n * i^r - 1 and its inverse: Z_H is constant on a coset
         Fr comb_i, comb_g1, comb_g2;  // quotient_combine_kernel's constants: i = mu^n, 1 / g^n, 1 / g^2n
         // Public inputs are the only non-zero entries of the PI column (prover.py:57-62): with few of them PI's
         // coefficient and coset forms are cheaper from the Lagrange basis directly than through two transforms.
@@ -100,6 +103,7 @@ struct plonk_prover {
     } circuit;
     plonk_srs* lag_srs;   // plonk_prover_set_options: Lagrange-basis view of srs (PLONK_PROVER_LAGRANGE_COMMITS), owned by srs
     unsigned seg_forced;  // PLONK_PROVER_SEGMENTS_LOG2: k + 1 forces S = 2^k, 0 = prover_plan_segments
+    bool blinding;        // PLONK_PROVER_BLINDING
     unsigned solve_forced;  // PLONK_PROVER_SOLVE_FORM: PLONK_PROVER_SOLVE_LANES or PLONK_PROVER_SOLVE_LEVELS for every input upload, 0 = solve_plan_form
     // ---- what the five rounds read and write: per-batch buffers (capacity cap_b proofs; prover.hip: batch_buffers)
     struct Rounds {
@@ -113,6 +117,7 @@ struct plonk_prover {
         uint32_t* closes;  // [2][B]  [0]: Z closes to 1 (round 2); [1]: a gate row fails (gate_check_kernel)
         Fr *wz;        // [2][B][n]  W_z, W_zw coefficient forms
         struct LinWeights* lin_w;  // [B]   round-5 linearisation weights
+        struct BlindState* blind;  // [B]   the blinders and the tails they give (prover_blind.h); unused without PLONK_PROVER_BLINDING
         // the segmented scans (prover_scans.h): carries and partial sums of the S segments of every proof, none while S = 1
         Fr* seg;                   // [scan_scratch_elems(B, S)]
         size_t seg_cap;            // elements
@@ -151,6 +156,16 @@ struct plonk_prover {
         uint32_t* bad;             // [B] 0, or 1 + the first row whose check failed (capacity: intake.inputs.cap proofs)
         bool valid;                // the resident batch came through the solver: `bad` belongs to it
     } solver;
+    // ---- blinding (prover_blind.h): where a run's blinders come from.  They belong to a RUN, not to an intake slot
+    struct Blinding {
+        struct G1Affine* htab;     // [6][16] 2^(16 w) ([tau^(n+k)] - [tau^k]); built when the option is switched on
+        Fr* explicit_b;            // [explicit_cap][11] plonk_prover_set_blinders (Montgomery, device)
+        size_t explicit_cap;       // proofs explicit_b holds
+        size_t explicit_batch;     // batch the pending explicit blinders were set for, 0: none pending
+        bool seeded;               // plonk_prover_seed_blinders has been called
+        uint8_t seed[32];
+        unsigned long long runs;   // blinded runs since the seed was set
+    } blinding_src;
     // ---- results: per-batch buffers like the rounds'
     struct Results {
         Fq *commit_xy; // [9][B] x||y canonical

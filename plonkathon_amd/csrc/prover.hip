@@ -6,7 +6,8 @@
 // that a whole batch is one uninterrupted stream of kernel launches with no host round trip.
 //
 // Every committed polynomial is uniquely determined by (circuit, witness, challenges) — the
-// reference adds no blinding (README.md:31-32) — so the schedule is free to differ from the
+// reference adds no blinding (README.md:31-32); PLONK_PROVER_BLINDING adds the PLONK paper's as correction launches beside these
+// kernels (prover_blind.h) — so the schedule is free to differ from the
 // reference's as long as the polynomials are the same:
 //   * the coset offset used for the quotient is a FIXED generator g = 5 instead of the per-proof
 //     `fft_cofactor` challenge (which is still drawn, to keep the transcript identical); the
@@ -20,11 +21,13 @@
 #include <string.h>
 
 #include <array>
+#include <vector>
 
 #include "prover.h"
 #include "g1_codec.h"
 #include "prover_scans.h"  // rounds 2, 4 and 5: the grand product, the evaluations, the divisions — kernels and launchers
 #include "prover_intake.h"  // a batch from the caller's bytes to resident witnesses: the uploads, the wiring, the witness solver
+#include "prover_blind.h"  // PLONK_PROVER_BLINDING: the blinders, the tails and every correction they add beside the kernels of this file
 
 // ------------------------------------------------------------------------------------------------
 // Sparse public inputs.  PI = sum_{i < l} (-pub_i) L_i with L_i the Lagrange basis of the n-th roots of unity:
@@ -358,13 +361,14 @@ static unsigned prover_segments(const plonk_prover* p, size_t B) {
 // holds n_vectors Fr vectors of n elements and `bytes` more; `extra` bytes once.  in_set: the buffer belongs to the resident batch's set
 // (prover_intake.h): an advance exchanges it with the staged set's, which staged_grow sizes on its own.
 struct BatchBuffer { void** slot; size_t n_vectors, bytes, extra; bool in_set; };
-#define BATCH_N_VECTORS 32  // 32 n-vectors of 32 bytes per proof: the figure of the out-of-memory message
-static std::array<BatchBuffer, 13> batch_buffers(plonk_prover* p) {
+// n-vectors of 32 bytes per proof, the figure of the out-of-memory message: 32, or 37 on the four cosets of a blinded prover
+static size_t batch_n_vectors(const plonk_prover* p) { return 17 + 5 * p->circuit.qcosets; }
+static std::array<BatchBuffer, 14> batch_buffers(plonk_prover* p) {
     plonk_prover::Rounds& r = p->rounds;
     plonk_prover::Results& o = p->results;
     const size_t e = sizeof(Fr);
-    return {{{(void**)&r.wit_lag, STAGED_N_VECTORS, 0, 0, true}, {(void**)&r.z_lag, 1}, {(void**)&r.coef, 5}, {(void**)&r.big, 5 * QCOSETS}, {(void**)&r.quot, 4},
-             {(void**)&r.num, 1}, {(void**)&r.wz, 2}, {(void**)&r.closes, 0, 2 * sizeof(uint32_t)}, {(void**)&r.lin_w, 0, sizeof(LinWeights)},
+    return {{{(void**)&r.wit_lag, STAGED_N_VECTORS, 0, 0, true}, {(void**)&r.z_lag, 1}, {(void**)&r.coef, 5}, {(void**)&r.big, 5 * p->circuit.qcosets}, {(void**)&r.quot, 4},
+             {(void**)&r.num, 1}, {(void**)&r.wz, 2}, {(void**)&r.closes, 0, 2 * sizeof(uint32_t)}, {(void**)&r.lin_w, 0, sizeof(LinWeights)}, {(void**)&r.blind, 0, sizeof(BlindState)},
              {(void**)&o.commit_xy, 0, PROOF_POINTS * 2 * sizeof(Fq)}, {(void**)&o.commit_flags, 0, PROOF_POINTS},
              {(void**)&o.state, 0, sizeof(ProofState)}, {(void**)&p->intake.pub, 0, p->circuit.n_public * e, e, true}}};
 }
@@ -397,12 +401,12 @@ static int ensure_buffers(plonk_prover* p, size_t B, bool rounds_only) {
         if (rc == PLONK_OK && !(rounds_only && b.in_set)) rc = dev_alloc(b.slot, B * (b.n_vectors * p->circuit.n * sizeof(Fr) + b.bytes) + b.extra);
         vectors += b.n_vectors;
     }
-    assert(vectors == BATCH_N_VECTORS);
+    assert(vectors == batch_n_vectors(p));
     if (rc != PLONK_OK) {
         free_batch(p, rounds_only);
         if (rc == PLONK_ERR_NOMEM)
             plonk_set_error("a batch of %zu proofs of group_order %zu needs %zu bytes of device memory", B, p->circuit.n,
-                            BATCH_N_VECTORS * B * p->circuit.n * sizeof(Fr));
+                            batch_n_vectors(p) * B * p->circuit.n * sizeof(Fr));
         return rc;
     }
     p->rounds.cap_b = B;
@@ -424,6 +428,34 @@ static int commit(plonk_prover* p, size_t B, const Fr* lag, const Fr* coef, size
     const plonk_prover::Circuit& c = p->circuit;
     return msm_run_device(c.ctx, p->lag_srs ? p->lag_srs : c.srs, p->lag_srs ? lag : coef, c.n, count * B, c.n, p->results.commit_xy + 2 * first_point * B,
                           p->results.commit_flags + first_point * B);
+}
+
+// sum_k q_k H_k into `count` x B commitments of the proof records from `first_point` on, behind the MSMs that left MSM(p0) there
+static void blind_commit(plonk_prover* p, size_t B, unsigned first_point, unsigned count) {
+    PLONK_LAUNCH(blind_commit_kernel, dim3((unsigned)B, count), dim3(BLIND_LANES), 0, p->circuit.ctx->stream, (const BlindState*)p->rounds.blind,
+                 (const G1Affine*)p->blinding_src.htab, first_point, B, p->results.commit_xy, p->results.commit_flags);
+}
+
+// The blinders of this run into the BlindStates: the explicit ones where plonk_prover_set_blinders left some for this batch size
+// (they serve one run), the seed's draws otherwise.  Every blinded run counts, so that one seed never blinds two batches alike.
+static int blinders_for_run(plonk_prover* p, size_t B) {
+    plonk_prover::Blinding& bl = p->blinding_src;
+    hipStream_t s = p->circuit.ctx->stream;
+    PLONK_REQUIRE(!bl.explicit_batch || bl.explicit_batch == B, PLONK_ERR_STATE, "run: batch %zu, but the blinders were set for a batch of %zu", B,
+                  bl.explicit_batch);
+    PLONK_REQUIRE(bl.explicit_batch || bl.seeded, PLONK_ERR_STATE,
+                  "run: batch %zu is to be blinded, but neither plonk_prover_set_blinders nor plonk_prover_seed_blinders has been called", B);
+    if (bl.explicit_batch) {
+        PLONK_LAUNCH(blind_load_kernel, grid1(B * BLIND_COUNT), dim3(256), 0, s, (const Fr*)bl.explicit_b, B, p->rounds.blind);
+        bl.explicit_batch = 0;
+    } else {
+        BlindSeed in;
+        memcpy(in.seed, bl.seed, 32);
+        in.run = bl.runs;
+        PLONK_LAUNCH(blind_derive_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, s, in, B, p->circuit.chal, p->rounds.blind);
+    }
+    bl.runs++;
+    return PLONK_OK;
 }
 
 static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32, size_t n_public);
@@ -452,6 +484,80 @@ int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const ui
 
 }  // extern "C"
 
+// Everything of the circuit that lives on the cosets g mu^r H, r < qcosets, anew: plonk_prover_create for three, and
+// plonk_prover_set_options when PLONK_PROVER_BLINDING changes their number.
+static void free_coset_tables(plonk_prover::Circuit& c) {
+    dev_free_all({(void**)&c.fixed_big, (void**)&c.l0_big, (void**)&c.x_big, (void**)&c.g_pow, (void**)&c.ginv_pow, (void**)&c.li_big});
+}
+static int coset_tables(plonk_prover* p) {
+    plonk_prover::Circuit& c = p->circuit;
+    plonk_ctx* ctx = c.ctx;
+    const size_t n = c.n, e = sizeof(Fr), n3 = c.qcosets * n;
+    const unsigned log_n = c.log_n;
+    free_coset_tables(c);
+    PLONK_TRY(dev_alloc((void**)&c.fixed_big, 8 * n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.l0_big, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.x_big, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.g_pow, n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.ginv_pow, n3 * e));
+    const Fr one = fp_one<FrParams>();
+    const Fr mu = host_root_of_unity(log_n + 2, false);
+    Fr base = c.g;  // g mu^r
+    for (unsigned r = 0; r < c.qcosets; r++) {
+        PLONK_TRY(k_fr_powers(ctx, base, one, c.g_pow + r * n, n));
+        PLONK_TRY(k_fr_powers(ctx, fp_inv(base), fp_mul(c.half, c.n_inv), c.ginv_pow + r * n, n));
+        PLONK_TRY(k_fr_powers(ctx, c.w, base, c.x_big + r * n, n));
+        base = fp_mul(base, mu);
+    }
+    // the circuit polynomials' values on the cosets: P(g mu^r w^j) is the size-n transform of c_i (g mu^r)^i
+    const NttFan fan{c.qcosets, 0u, (unsigned)n, (unsigned)n};
+    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8, n, n, n3, c.g_pow, nullptr, false, &fan));
+    // L0: Lagrange vector e_0 has coefficient form (1/n, 1/n, ...)          prover.py:184-186
+    void* tmpv;
+    PLONK_TRY(ctx_scratch(ctx, 2, n * e, &tmpv));  // context-owned scratch: nothing to leak on an error path
+    Fr* tmp = (Fr*)tmpv;
+    PLONK_TRY(k_fr_powers(ctx, one, c.n_inv, tmp, n));
+    PLONK_TRY(ntt_run(ctx, tmp, c.l0_big, log_n, false, 1, n, n, n3, c.g_pow, nullptr, false, &fan));
+    if (c.sparse_pi && c.n_public) {
+        Zh4 zh4;
+        for (int k = 0; k < 4; k++) zh4.v[k] = c.zh[k];
+        PLONK_TRY(dev_alloc((void**)&c.li_big, c.n_public * n3 * e));
+        PLONK_LAUNCH(li_coset_kernel, grid1(c.n_public * n3), dim3(256), 0, ctx->stream, (const Fr*)c.x_big, c.roots, n3, n, c.n_public,
+                     zh4, c.n_inv, c.li_big);
+        PLONK_CHECK_HIP(hipGetLastError());
+    }
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return PLONK_OK;
+}
+
+// PLONK_PROVER_BLINDING on or off (prover_blind.h).  The quotient of a blinded proof has 3n + 6 coefficients, so it is interpolated
+// from four cosets, which takes n >= 8 (3n + 5 < 4n); its commitments add multiples of [tau^(n+k)] - [tau^k], k < 6, which takes
+// n + 6 monomial powers.  The coset forms are rebuilt for the new number of cosets and the per-batch buffers are dropped (r.big
+// changes size): the resident batch goes with them, a staged one stays.
+static int set_blinding(plonk_prover* p, bool on) {
+    plonk_prover::Circuit& c = p->circuit;
+    plonk_prover::Blinding& bl = p->blinding_src;
+    if (on) {
+        PLONK_REQUIRE(c.n >= 8, PLONK_ERR_ARG, "blinding: the quotient has 3n + 6 coefficients and four cosets hold 4n: group_order %zu is below 8", c.n);
+        const plonk_srs* mono = c.srs->parent ? c.srs->parent : c.srs;  // a Lagrange view (plonk_srs_lagrange) takes the powers from its monomial parent
+        PLONK_REQUIRE(mono->bases, PLONK_ERR_ARG, "blinding: the prover's SRS holds no monomial powers; the blinded commitments need tau^%zu .. tau^%zu",
+                      c.n, c.n + BLIND_TAIL - 1);
+        PLONK_REQUIRE(mono->n_points >= c.n + BLIND_TAIL, PLONK_ERR_ARG, "blinding: group_order %zu needs %zu powers of tau, the SRS has %zu", c.n,
+                      c.n + BLIND_TAIL, mono->n_points);
+        if (!bl.htab) {
+            PLONK_TRY(dev_alloc((void**)&bl.htab, BLIND_TAIL * BLIND_WINDOWS * sizeof(G1Affine)));
+            PLONK_LAUNCH(blind_h_kernel, dim3(2), dim3(64), 0, c.ctx->stream, (const G1Affine*)mono->bases, c.n, bl.htab);
+            PLONK_CHECK_HIP(hipGetLastError());
+        }
+    }
+    PLONK_CHECK_HIP(hipStreamSynchronize(c.ctx->stream));
+    free_batch(p);
+    c.qcosets = on ? QCOSETS_BLINDED : QCOSETS;
+    PLONK_TRY(coset_tables(p));
+    p->blinding = on;
+    return PLONK_OK;
+}
+
 static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
                        size_t n_public) {
     const size_t n = (size_t)1 << log_n;
@@ -469,72 +575,44 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
     const size_t e = sizeof(Fr);
     PLONK_TRY(dev_alloc((void**)&c.fixed_lag, 8 * n * e));
     PLONK_TRY(dev_alloc((void**)&c.fixed_coef, 8 * n * e));
-    const size_t n3 = QCOSETS * n;
-    PLONK_TRY(dev_alloc((void**)&c.fixed_big, 8 * n3 * e));
-    PLONK_TRY(dev_alloc((void**)&c.l0_big, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&c.x_big, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&c.g_pow, n3 * e));
-    PLONK_TRY(dev_alloc((void**)&c.ginv_pow, n3 * e));
     PLONK_TRY(plonk_fr_upload(ctx, c.fixed_lag, selectors_le32, 8 * n));
     PLONK_TRY(intake_init(p, selectors_le32));
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &c.roots));
-    const Fr one = fp_one<FrParams>();
-    const Fr mu = host_root_of_unity(log_n + 2, false);
-    Fr base = c.g;  // g mu^r
-    for (unsigned r = 0; r < QCOSETS; r++) {
-        PLONK_TRY(k_fr_powers(ctx, base, one, c.g_pow + r * n, n));
-        PLONK_TRY(k_fr_powers(ctx, fp_inv(base), fp_mul(c.half, c.n_inv), c.ginv_pow + r * n, n));
-        PLONK_TRY(k_fr_powers(ctx, c.w, base, c.x_big + r * n, n));
-        base = fp_mul(base, mu);
-    }
-    // coefficient forms of the 8 circuit polynomials, and their values on the three cosets: P(g mu^r w^j) is the size-n
-    // transform of c_i (g mu^r)^i
+    // coefficient forms of the 8 circuit polynomials
     PLONK_TRY(ntt_run(ctx, c.fixed_lag, c.fixed_coef, log_n, true, 8, n, n, n, nullptr, nullptr, true));
-    const NttFan fan{QCOSETS, 0u, (unsigned)n, (unsigned)n};
-    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8, n, n, n3, c.g_pow, nullptr, false, &fan));
-    // L0: Lagrange vector e_0 has coefficient form (1/n, 1/n, ...)          prover.py:184-186
-    void* tmpv;
-    PLONK_TRY(ctx_scratch(ctx, 2, n * e, &tmpv));  // context-owned scratch: nothing to leak on an error path
-    Fr* tmp = (Fr*)tmpv;
-    PLONK_TRY(k_fr_powers(ctx, one, c.n_inv, tmp, n));
-    PLONK_TRY(ntt_run(ctx, tmp, c.l0_big, log_n, false, 1, n, n, n3, c.g_pow, nullptr, false, &fan));
-    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     // Z_H on coset r is the constant (g mu^r)^n - 1 = g^n i^r - 1, i = mu^n            prover.py:178
+    const Fr one = fp_one<FrParams>();
     Fr gn = c.g;
     for (unsigned i = 0; i < log_n; i++) gn = fp_sqr(gn);
     Fr i4 = host_root_of_unity(2, false), cur = gn;
-    Zh4 zh4;
     for (int k = 0; k < 4; k++) {
-        zh4.v[k] = fp_sub(cur, one);
-        if (k < QCOSETS) c.zh_inv[k] = fp_inv(zh4.v[k]);
+        c.zh[k] = fp_sub(cur, one);
+        c.zh_inv[k] = fp_inv(c.zh[k]);
         cur = fp_mul(cur, i4);
     }
     c.comb_i = i4;
     c.comb_g1 = fp_inv(gn);
     c.comb_g2 = fp_mul(fp_sqr(c.comb_g1), c.half);
     c.sparse_pi = n_public <= PI_SPARSE_MAX;
-    if (c.sparse_pi && n_public) {
-        PLONK_TRY(ntt_get_roots(ctx, log_n, true, &c.roots_inv));
-        PLONK_TRY(dev_alloc((void**)&c.li_big, n_public * n3 * e));
-        PLONK_LAUNCH(li_coset_kernel, grid1(n_public * n3), dim3(256), 0, ctx->stream, (const Fr*)c.x_big, c.roots, n3, n, n_public,
-                     zh4, c.n_inv, c.li_big);
-        PLONK_CHECK_HIP(hipGetLastError());
-        PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
+    if (c.sparse_pi && n_public) PLONK_TRY(ntt_get_roots(ctx, log_n, true, &c.roots_inv));
+    c.qcosets = QCOSETS;
+    PLONK_TRY(coset_tables(p));
     return PLONK_OK;  // (the MSM tables are built by the first commitment: lookup table or bucket-method window table)
 }
 
 extern "C" {
 
 int plonk_prover_set_options(plonk_prover* p, unsigned flags) {
-    PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK | PLONK_PROVER_SOLVE_FORM_MASK)), PLONK_ERR_ARG,
-                  "unknown prover option bits %#x", flags);
+    PLONK_REQUIRE(p && !(flags & ~(PLONK_PROVER_LAGRANGE_COMMITS | PLONK_PROVER_SEGMENTS_MASK | PLONK_PROVER_SOLVE_FORM_MASK | PLONK_PROVER_BLINDING)),
+                  PLONK_ERR_ARG, "unknown prover option bits %#x", flags);
     PLONK_ENTER(p->circuit.ctx);
     const unsigned seg = (flags & PLONK_PROVER_SEGMENTS_MASK) >> 8;  // k + 1, 0 = automatic
     PLONK_REQUIRE(seg <= 9 && (!seg || (p->circuit.n >> (seg - 1)) >= 16), PLONK_ERR_ARG,
                   "2^%u segments: at most 256, of at least 16 rows each (group_order %zu)", seg ? seg - 1 : 0, p->circuit.n);
     const unsigned form = (flags & PLONK_PROVER_SOLVE_FORM_MASK) >> 16;  // 0 = automatic
     PLONK_REQUIRE(form <= PLONK_PROVER_SOLVE_LEVELS, PLONK_ERR_ARG, "solve form %u: 0 (automatic), 1 (one lane per proof) or 2 (levels)", form);
+    const bool blinding = (flags & PLONK_PROVER_BLINDING) != 0;
+    if (blinding != p->blinding) PLONK_TRY(set_blinding(p, blinding));
     p->seg_forced = seg;
     p->solve_forced = form;  // from the next input upload on
     p->lag_srs = nullptr;
@@ -551,8 +629,8 @@ int plonk_prover_destroy(plonk_prover* p) {
         if (c.ctx->copy_stream) hipStreamSynchronize(c.ctx->copy_stream);  // a batch that is still staged: its solve reads the circuit and the plan
     }
     free_batch(p);
-    dev_free_all({(void**)&c.fixed_lag, (void**)&c.fixed_coef, (void**)&c.fixed_big, (void**)&c.l0_big, (void**)&c.x_big, (void**)&c.g_pow,
-                  (void**)&c.ginv_pow, (void**)&c.li_big});
+    free_coset_tables(c);
+    dev_free_all({(void**)&c.fixed_lag, (void**)&c.fixed_coef, (void**)&p->blinding_src.htab, (void**)&p->blinding_src.explicit_b});
     intake_destroy(p);
     delete p;
     return PLONK_OK;
@@ -575,6 +653,9 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_REQUIRE(B <= 65535, PLONK_ERR_ARG, "batch %zu exceeds 65535 (the proofs are a grid's second dimension)", B);
     PLONK_TRY(ensure_segments(p, B));  // (the options may have changed since the upload)
     const unsigned S = prover_segments(p, B);  // of the three scans (prover_scans.h); 1: one workgroup per proof
+    const bool blind = p->blinding;            // every `if (blind)` below is a correction of prover_blind.h behind the step it follows
+    BlindState* bs = r.blind;
+    if (blind) PLONK_TRY(blinders_for_run(p, B));
 
     transcript_round(p, B, 0);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
@@ -589,6 +670,7 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
         PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 4 * B, n, n, n, nullptr, nullptr, true));
     }
     PLONK_TRY(commit(p, B, r.wit_lag, r.coef, 3, 0));
+    if (blind) blind_commit(p, B, 0, 3);
     transcript_round(p, B, 1);
     // ---- round 2: grand product Z, commit                                      prover.py:121-152
     GrandProductIn gp;
@@ -602,13 +684,16 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_TRY(prof_end(ctx));
     PLONK_TRY(ntt_run(ctx, r.z_lag, r.coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
     PLONK_TRY(commit(p, B, r.z_lag, r.coef + 4 * B * n, 1, 3));
+    if (blind) blind_commit(p, B, 3, 1);
     transcript_round(p, B, 2);
     // ---- round 3: coset extensions, fused quotient, back to coefficients, commit T1..T3   prover.py:154-226
     // deg t < 3n: three cosets g mu^r H of the n-th roots of unity determine the quotient, so A, B, C, Z are evaluated on 3n
     // points — per coset a size-n transform of c_i (g mu^r)^i, on the 2^log_n kernel — instead of the reference's 4n, the
-    // fused pass runs over 3n points, and three size-n inverse transforms + quotient_combine_kernel give T1, T2, T3
-    const size_t n3 = QCOSETS * n;
-    const NttFan fan{QCOSETS, 0u, (unsigned)n, (unsigned)n};  // one input, three scalings (g mu^r)^i, outputs [r][n] side by side
+    // fused pass runs over 3n points, and three size-n inverse transforms + quotient_combine_kernel give T1, T2, T3.
+    // Blinded, deg t = 3n + 5: the same on all four cosets (n3 = 4n), the tails' values added to the coset forms in between, and
+    // blind_combine_kernel in quotient_combine_kernel's place.
+    const size_t n3 = c.qcosets * n;
+    const NttFan fan{c.qcosets, 0u, (unsigned)n, (unsigned)n};  // one input, three scalings (g mu^r)^i, outputs [r][n] side by side
     if (c.sparse_pi) {  // A, B, C and Z through the transform, PI from the Lagrange basis on the coset
         PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 3 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
         PLONK_TRY(ntt_run(ctx, r.coef + 4 * B * n, r.big + 4 * B * n3, log_n, false, B, n, n, n3, c.g_pow, nullptr, false, &fan));
@@ -617,8 +702,13 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     } else {
         PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 5 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
     }
+    if (blind) {
+        BlindZh bz;
+        for (int k = 0; k < 4; k++) bz.v[k] = c.zh[k];
+        PLONK_LAUNCH(blind_coset_kernel, grid1(B * n3), dim3(256), 0, s, (const BlindState*)bs, (const Fr*)c.x_big, bz, log_n, B, r.big);
+    }
     ZhInv zh;
-    for (int k = 0; k < 4; k++) zh.v[k] = c.zh_inv[k < QCOSETS ? k : 0];
+    for (int k = 0; k < 4; k++) zh.v[k] = c.zh_inv[k < (int)c.qcosets ? k : 0];
     QuotientIn qi;
     for (int k = 0; k < 5; k++) qi.wit[k] = r.big + (size_t)k * B * n3;
     for (int k = 0; k < FX_COUNT; k++) qi.fixed[k] = c.fixed_big + (size_t)k * n3;
@@ -626,27 +716,67 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     qi.xs = c.x_big;
     PLONK_LAUNCH(quotient_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)B), dim3(256), 0, s, qi, zh, (const ProofState*)state, RoundChallenges{},
                  (unsigned)n3, r.quot, log_n, (unsigned)n4);
-    const NttFan slices{QCOSETS, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
+    const NttFan slices{c.qcosets, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
     PLONK_TRY(ntt_run(ctx, r.quot, r.quot, log_n, true, B, n, n4, n4, nullptr, c.ginv_pow, false, &slices));
-    PLONK_LAUNCH(quotient_combine_kernel, grid1(B * n), dim3(256), 0, s, r.quot, n, n4, B, c.comb_i, c.comb_g1, c.comb_g2, c.half);
+    if (blind) {
+        const BlindCombine bc = {c.comb_i, c.half, fp_mul(c.comb_g1, c.half), c.comb_g2, fp_mul(c.comb_g2, c.comb_g1)};
+        PLONK_LAUNCH(blind_combine_kernel, grid1(B * n), dim3(256), 0, s, r.quot, n, n4, B, bc, bs);
+    } else {
+        PLONK_LAUNCH(quotient_combine_kernel, grid1(B * n), dim3(256), 0, s, r.quot, n, n4, B, c.comb_i, c.comb_g1, c.comb_g2, c.half);
+    }
     // T1..T3 = the three n-coefficient slices of each quotient row, one batched call (MSM k*B + b = slice k of proof b)
     PLONK_TRY(msm_run_device(ctx, c.srs, r.quot, n, 3 * B, n4, p->results.commit_xy + 2 * 4 * B, p->results.commit_flags + 4 * B, B, n));
+    if (blind) blind_commit(p, B, 4, 3);
     transcript_round(p, B, 3);
     // ---- round 4: evaluations                                                  prover.py:228-239
     PLONK_TRY(prof_begin(ctx, "prover_evaluations", 7.0 * 32.0 * (double)n * (double)B));
     PLONK_TRY(scan_evaluations(s, S, r.coef, c.fixed_coef, c.w, state, n, B, r.seg));
     PLONK_TRY(prof_end(ctx));
+    if (blind) PLONK_LAUNCH(blind_evals_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const BlindState*)bs, state, c.w, log_n, B);
     transcript_round(p, B, 4);
     // ---- round 5: opening polynomials in coefficient form, commit              prover.py:241-306
     PLONK_LAUNCH(linearisation_weights_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const ProofState*)state, log_n, c.n_inv, B, r.lin_w);
     PLONK_LAUNCH(linearisation_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, (const Fr*)r.coef, (const Fr*)c.fixed_coef,
                  (const Fr*)r.quot, (const LinWeights*)r.lin_w, log_n, B, r.num);
+    if (blind) PLONK_LAUNCH(blind_openings_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, bs, (const ProofState*)state, (const Fr*)r.lin_w, c.w, B);
     PLONK_TRY(prof_begin(ctx, "prover_divisions", 2.0 * 3.0 * 32.0 * (double)n * (double)B));
     const DivideIn dv = {{r.num, r.coef + 4 * B * n}, {r.wz, r.wz + B * n}};  // W_z's numerator by X - zeta, Z by X - zeta w
     PLONK_TRY(scan_divisions(s, S, dv, c.w, state, n, B, r.seg));
     PLONK_TRY(prof_end(ctx));
+    if (blind)
+        PLONK_LAUNCH(blind_division_kernel, dim3((unsigned)((n + 256 * BLIND_ROWS_PER_LANE - 1) / (256 * BLIND_ROWS_PER_LANE)), (unsigned)B, 2), dim3(256), 0, s,
+                     (const BlindState*)bs, (const ProofState*)state, c.w, n, B, r.wz);
     PLONK_TRY(msm_run_device(ctx, c.srs, r.wz, n, 2 * B, n, p->results.commit_xy + 2 * 7 * B, p->results.commit_flags + 7 * B));
+    if (blind) blind_commit(p, B, 7, 2);
     PLONK_CHECK_HIP(hipGetLastError());
+    return PLONK_OK;
+}
+
+// The blinders of the next blinded run of `batch` proofs, [batch][11] canonical LE: b[0..10] of prover_blind.h's table.
+int plonk_prover_set_blinders(plonk_prover* p, const uint8_t* blinders_le32, size_t batch) {
+    PLONK_REQUIRE(p && blinders_le32 && batch, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(p->circuit.ctx);
+    plonk_prover::Blinding& bl = p->blinding_src;
+    const size_t count = batch * BLIND_COUNT;
+    for (size_t i = 0; i < count; i++)
+        PLONK_REQUIRE(le32_below_modulus(blinders_le32 + 32 * i, false), PLONK_ERR_ARG, "blinder %zu of proof %zu is not below r", i % BLIND_COUNT,
+                      i / BLIND_COUNT);
+    hipStream_t s = p->circuit.ctx->stream;
+    PLONK_TRY(dev_grow(s, &bl.explicit_cap, batch, {{(void**)&bl.explicit_b, count * sizeof(Fr)}}));
+    std::vector<Fr> mont(count);
+    for (size_t i = 0; i < count; i++) mont[i] = fr_from_le32(blinders_le32 + 32 * i);
+    PLONK_CHECK_HIP(hipMemcpyAsync(bl.explicit_b, mont.data(), count * sizeof(Fr), hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipStreamSynchronize(s));  // `mont` goes out of scope
+    bl.explicit_batch = batch;
+    return PLONK_OK;
+}
+
+// The device draws every later run's blinders from `seed`, the number of blinded runs since this call and the proof's index.
+int plonk_prover_seed_blinders(plonk_prover* p, const uint8_t seed[32]) {
+    PLONK_REQUIRE(p && seed, PLONK_ERR_ARG, "bad argument");
+    memcpy(p->blinding_src.seed, seed, 32);
+    p->blinding_src.seeded = true;
+    p->blinding_src.runs = 0;
     return PLONK_OK;
 }
 

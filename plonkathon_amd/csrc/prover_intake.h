@@ -1,6 +1,8 @@
 // prover_intake.h — how a batch gets into the lock-step prover (internal, included by prover.hip): everything between "bytes from
 // the caller" and "wit_lag, pub, the PI column and resident_b are in place".  The wiring and the solver's plan, the three kinds
 // of upload (wire columns, per-variable values, input values), and what reads the resident variables back.
+// Blinding (prover_blind.h) is not intake: the blinders belong to a RUN, not to a slot — plonk_prover_run draws or copies them for
+// the batch it proves — so staging and advance are the same for a blinded prover.
 //
 // Stream order of an upload.  C = the context's compute stream, H = its copy stream; "sync" and "async" are the two entry points
 // of a kind.  Growing a buffer waits for C first (dev_grow).

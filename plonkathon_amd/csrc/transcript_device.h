@@ -142,6 +142,37 @@ PLONK_DEV void tc_append_message(TcState& t, TcShared& sh, unsigned lane, const 
     tc_absorb(t, sh, lane, msg, mlen);
 }
 
+// challenge_bytes(label, 255) read as a big-endian integer mod r (the reference's wide reduction: no bias), zero included and nothing
+// re-appended.  The 255 bytes stay in sh.msg; every lane of the group gets the value (Montgomery form).  (tc_draw below repeats
+// these lines, and round 0 of tc_round those of tc_open, on purpose: calling the shared halves from there changes the code of
+// transcript_kernel and verify_scalars_kernel — profiles/blinding_kernel_compare.txt.)
+PLONK_DEV Fr tc_challenge_wide(TcState& t, TcShared& sh, unsigned lane, const ChallengeConsts& cc, const char* label, unsigned llen) {
+    tc_frame(t, sh, lane, label, llen, 255);
+    tc_begin_op(t, sh, lane, STROBE_FLAG_I | STROBE_FLAG_A | STROBE_FLAG_C);
+    __syncthreads();  // earlier readers of sh.msg are done
+    tc_squeeze(t, sh, lane, sh.msg, 255);
+    __syncthreads();
+    if (lane < 8) {  // chunk 0 = the leading 31 bytes, chunk c >= 1 = the next 32; weight 2^(256 (7 - c))
+        const unsigned take = lane ? 32 : 31, off = lane ? 31 + 32 * (lane - 1) : 0;
+        Fr chunk;  // little-endian limbs of the big-endian chunk
+#pragma unroll
+        for (unsigned l = 0; l < 8; l++) {
+            uint32_t wv = 0;
+#pragma unroll
+            for (unsigned k = 0; k < 4; k++) {
+                const unsigned sig = 4 * l + k;  // byte significance within the chunk
+                if (sig < take) wv |= (uint32_t)sh.msg[off + take - 1 - sig] << (8 * k);
+            }
+            chunk.v[l] = wv;
+        }
+        sh.part[lane] = fp_mul(chunk, cc.c[7 - lane]);
+    }
+    __syncthreads();
+    Fr f = sh.part[0];
+    for (int k = 1; k < 8; k++) f = fp_add(f, sh.part[k]);
+    return f;
+}
+
 // transcript.py:69-75: 255 PRF bytes -> big-endian integer mod r (retry on zero) -> re-appended.  Returns the
 // challenge (Montgomery form) in every lane of the group.
 PLONK_DEV Fr tc_draw(TcState& t, TcShared& sh, unsigned lane, const ChallengeConsts& cc, const char* label, unsigned llen) {
@@ -174,6 +205,20 @@ PLONK_DEV Fr tc_draw(TcState& t, TcShared& sh, unsigned lane, const ChallengeCon
             return f;
         }
     }
+}
+
+// MerlinTranscript(label): the STROBE-128 state under "Merlin v1.0", then the domain separator
+PLONK_DEV void tc_open(TcState& t, TcShared& sh, unsigned lane, const char* label, unsigned llen) {
+    const uint8_t init[18] = {1, STROBE_R + 2, 1, 0, 1, 96, 'S', 'T', 'R', 'O', 'B', 'E', 'v', '1', '.', '0', '.', '2'};
+    t.w = 0;
+    for (unsigned j = 0; j < 8; j++)
+        if (8 * lane + j < 18) t.w |= (uint64_t)init[8 * lane + j] << (8 * j);
+    tc_keccak(t, sh, lane);
+    t.pos = 0;
+    t.pos_begin = 0;
+    tc_begin_op(t, sh, lane, STROBE_FLAG_M | STROBE_FLAG_A);
+    tc_absorb(t, sh, lane, (const uint8_t*)"Merlin v1.0", 11);
+    tc_append_message(t, sh, lane, "dom-sep", 7, (const uint8_t*)label, llen);
 }
 
 // The schedule.  Round 0 opens Transcript(b"plonk") (prover.py:53); rounds 1-4 are the prover's (transcript.py:77-116), round 5
