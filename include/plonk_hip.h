@@ -203,7 +203,13 @@ int plonk_g1_msm(plonk_ctx* ctx, plonk_srs* srs, const void* d_scalars, size_t n
  * explicit `bits` means the plain comb of h teeth, and mode | 32 the one with top tables (PLONK_ERR_ARG if h takes none).
  * mode | 64 (a TEST flag; only with mode 2 and a comb, PLONK_ERR_ARG with mode 0, mode 1 or | 16): the comb's accumulation kernel
  * runs in its 64-bit entry-index form whatever the table's size — the form that tables of more than 2^32 entries (275 GB) select
- * by themselves — so that it is reachable at toy sizes.  The table is the same one: the flag is no part of its identity. */
+ * by themselves — so that it is reachable at toy sizes.  The table is the same one: the flag is no part of its identity.
+ * mode | 128 and mode | 256 (TEST flags under the same conditions as | 64; both together: PLONK_ERR_ARG; no part of the table's
+ * identity either): the comb accumulates in its ROW WALK (| 128: lanes over (MSM, column) rows, the whole chip on one base per
+ * step) or in its column-lane kernel (| 256) whatever the library's rule would choose — the rule takes the row walk for batches
+ * that fill half the chip's workgroup slots and never reads `groups` of plonk_msm_configure.  Only while | 128 is set is a non-zero
+ * `groups` the number of chunks the scalars are cut into (clipped to the number of scalars; 0: the rule's count), so that several
+ * chunks are reachable at toy sizes; without the flag `groups` keeps its meaning of workgroups per MSM. */
 int plonk_msm_lookup_configure(plonk_ctx* ctx, int mode, unsigned bits, size_t budget_bytes);
 /* bits (teeth h / window bits c) of the table currently attached to `srs` (0 = none: its MSMs use the bucket method) */
 int plonk_srs_lookup_bits(const plonk_srs* srs, unsigned* out_bits);
@@ -506,7 +512,9 @@ int plonk_ntt_set_split(plonk_ctx* ctx, unsigned log_n, unsigned log_r1);
 /* log2 R1 of the split in force for 2^log_n (ctx NULL: the library default, which is what the distributed transform
  * uses on every rank — its column / frequency-strided layouts are [R1][R2 / W] and [R2][R1 / W]) */
 int plonk_ntt_get_split(plonk_ctx* ctx, unsigned log_n, unsigned* out_log_r1);
-/* tuning knobs (0 = library default): window bits c and window-groups per MSM (bucket method) */
+/* tuning knobs (0 = library default): window bits c and window-groups per MSM (bucket method).  On the table methods `groups` is
+ * the number of workgroups one MSM is cut into; for the comb that is its column-lane kernel alone — the row walk's launch shape
+ * comes from the library's rule and does not read it (except under the test flag plonk_msm_lookup_configure mode | 128). */
 int plonk_msm_configure(plonk_ctx* ctx, unsigned window_bits, unsigned groups);
 /* the number of segments the lock-step prover (and plonk_fr_grand_product, batch = 1) cuts the per-proof scans of `batch` proofs
  * of 2^log_n rows into on ctx's device when PLONK_PROVER_SEGMENTS_LOG2 is not set: 1 = one workgroup per proof */

@@ -97,7 +97,9 @@ class Context:
         return ms.value
 
     def msm_configure(self, window_bits=0, groups=0):
-        """Bucket-method tuning knobs (0 = library default)."""
+        """Tuning knobs (0 = library default): the bucket method's window bits, and `groups` = workgroups per MSM (bucket method, window
+        tables, the comb's column-lane kernel).  The comb's row walk does not read `groups`; only under msm_lookup(walk="rows"), a
+        test flag, is it the row walk's chunk count."""
         check(self.L.plonk_msm_configure(self.handle, window_bits, groups))
 
     @contextlib.contextmanager
@@ -116,12 +118,14 @@ class Context:
                 if ntt_kind:
                     self.L.plonk_ntt_select_kernel(self.handle, 0)
 
-    def msm_lookup(self, mode=0, bits=0, budget_bytes=0, windows=False, top=False, wide=False):
+    def msm_lookup(self, mode=0, bits=0, budget_bytes=0, windows=False, top=False, wide=False, walk=None):
         """Table-MSM policy (include/plonk_hip.h): mode 0 auto, 1 off, 2 force `bits` for every base set; comb tables (bits =
         teeth; `top`: the comb of that many teeth with top tables) unless `windows` (bits = window bits: the layout of rounds
-        2 - 5, kept for comparison).  `wide` (tests; mode 2 and a comb only): the comb kernel's 64-bit entry index at any table size."""
-        check(self.L.plonk_msm_lookup_configure(self.handle, mode | (16 if windows else 0) | (32 if top else 0) | (64 if wide else 0), bits,
-                                                budget_bytes))
+        2 - 5, kept for comparison).  `wide` (tests; mode 2 and a comb only): the comb kernel's 64-bit entry index at any table size.
+        `walk` (tests; likewise): "rows" forces the comb's row walk — only then, and only if non-zero, msm_configure's `groups` is its chunk count — and "lanes"
+        its column-lane kernel; None leaves the choice to the library's rule."""
+        flags = (16 if windows else 0) | (32 if top else 0) | (64 if wide else 0) | {None: 0, "rows": 128, "lanes": 256}[walk]
+        check(self.L.plonk_msm_lookup_configure(self.handle, mode | flags, bits, budget_bytes))
 
     def profile(self, on):
         check(self.L.plonk_profile_enable(self.handle, 1 if on else 0))

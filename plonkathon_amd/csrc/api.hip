@@ -698,11 +698,14 @@ int plonk_srs_lookup_top(const plonk_srs* srs, unsigned* out_top_bits, unsigned*
 int plonk_msm_lookup_configure(plonk_ctx* ctx, int mode, unsigned bits, size_t budget_bytes) {
     PLONK_REQUIRE(ctx, PLONK_ERR_ARG, "ctx is NULL");
     PLONK_ENTER(ctx);
-    const bool windows = (mode & 16) != 0, top = (mode & 32) != 0, wide = (mode & 64) != 0;
-    mode &= ~(16 | 32 | 64);
+    const bool windows = (mode & 16) != 0, top = (mode & 32) != 0, wide = (mode & 64) != 0, walk_rows = (mode & 128) != 0, walk_lanes = (mode & 256) != 0;
+    mode &= ~(16 | 32 | 64 | 128 | 256);
     PLONK_REQUIRE(mode >= 0 && mode <= 2, PLONK_ERR_ARG,
                   "mode must be 0 (auto), 1 (off) or 2 (force), optionally + 16 (window tables) or + 32 (the comb of `bits` teeth with top tables)");
     PLONK_REQUIRE(!wide || (mode == 2 && !windows), PLONK_ERR_ARG, "mode + 64 (the comb kernel's 64-bit entry index: tests) needs mode 2 and a comb (not + 16)");
+    PLONK_REQUIRE((!walk_rows && !walk_lanes) || (mode == 2 && !windows), PLONK_ERR_ARG,
+                  "mode + 128 / + 256 (the comb's row walk / its column-lane kernel: tests) need mode 2 and a comb (not + 16)");
+    PLONK_REQUIRE(!(walk_rows && walk_lanes), PLONK_ERR_ARG, "mode + 128 and + 256 exclude each other");
     PLONK_REQUIRE(!top || (!windows && bits && msm_comb_takes_top(bits)), PLONK_ERR_ARG,
                   "mode + 32 needs a comb (not + 16) of an explicit number of teeth with 254 mod teeth = 1 or 2 (7, 9, 11, 12, 14, 18, 21, 23 ..)");
     const unsigned max_bits = windows ? 17u : 24u;
@@ -713,6 +716,7 @@ int plonk_msm_lookup_configure(plonk_ctx* ctx, int mode, unsigned bits, size_t b
     ctx->msm_lookup_bits = bits;
     ctx->msm_lookup_top = top;
     ctx->msm_comb_wide = wide;
+    ctx->msm_comb_walk = walk_rows ? 1u : walk_lanes ? 2u : 0u;
     ctx->msm_lookup_budget = budget_bytes;
     return PLONK_OK;
 }

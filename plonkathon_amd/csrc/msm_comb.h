@@ -33,6 +33,9 @@
 //                               ("piece") in LDS per column they touch.  Every lane performs p additions (+-0): 104 for 2^11
 //                               scalars in 13 columns.  The pieces are tree-reduced per column through LDS; the workgroup
 //                               stores a column sums.
+//   msm_comb_rows_kernel        the accumulation of a BATCH (the row walk; msm_run_comb's rule chooses): lanes bound to (MSM, column)
+//                               rows, a workgroup = 256 consecutive rows x one chunk of the scalars, the whole chip on one base's
+//                               block per step; digits item-major; no LDS, no tree.  msm_comb_rowsum_kernel adds a row's chunks.
 //   msm_comb_colsum_kernel      (only when an MSM is cut into >= 4 workgroups) a wave per (MSM, column) sums the workgroups' sums
 //   msm_comb_finalize_kernel    sum_j 2^j S_j by Horner over groups of LPM lanes per MSM, deferred additions, unique affine form; an
 //                               addition of OPPOSITE operands gives the identity here (an MSM whose result is the identity — all
@@ -59,6 +62,7 @@ PLONK_HD bool msm_comb_needs_redo(uint32_t v) { return (v & MSM_COMB_REDO) != 0 
 // has it: a real scalar's digit is an index below 2^(h-1) <= 2^23 beside bit 31, and a virtual scalar's digit has bit 31 clear and
 // stays below (virtual (a - 1) + 1) << (h-1), which msm_comb_top_reach_ok keeps below 2^31 - ((a - 1) << (h-1)).
 #define MSM_COMB_SKIP 0xffffffffu
+struct alignas(16) MsmCombDigit4 { uint32_t d[4]; };  // four digits of consecutive rows: one 16-byte store (item-major layout)
 
 PLONK_HD unsigned msm_comb_columns(unsigned h) { return (MSM_COMB_SCALAR_BITS + h - 1) / h; }
 
@@ -272,16 +276,26 @@ __global__ void msm_comb_base_skip_kernel(const G1Affine* bases, size_t n, uint8
 // Items whose entry is the identity get MSM_COMB_SKIP: every column of an identity base (base_skip), and a group whose codes are all
 // zero — an identity base's code counts as zero, its share of every joint entry being the identity.  The kernel also zeroes
 // n_deferred[m]: it runs before the kernels that count.
+// Layout: the digit of (row = m A + j, item i) is digits[row * rs + i * is].  Column-major (rs, is) = (nd, 1) is what msm_comb_kernel
+// reads; item-major (1, R), R = M A rows, is the row walk's (msm_comb_rows_kernel): there a lane's A digits lie next to each other
+// and, where A is a multiple of four (every row then starts on 16 bytes), leave as 16-byte stores.
+// tsh: a workgroup takes 2^tsh MSMs (up to m_end) and 256 >> tsh scalars of each (whole groups), the MSM in the low bits of the lane
+// number.  0 for the column-major layout (a grid row per MSM); 2 for the item-major one, where the digits of one scalar in four
+// consecutive MSMs are 4 A consecutive words: lanes that wrote A words each, 4 R bytes apart, left every line partly written
+// (the kernel took twice its time).
 template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_digits_kernel(const Fr* scalars, size_t n, size_t stride, size_t inner,
-                                                                                              size_t outer_stride, size_t m0, uint32_t* digits, size_t nd,
+                                                                                              size_t outer_stride, size_t m0, size_t m_end, unsigned tsh,
+                                                                                              uint32_t* digits, size_t nd, size_t rs, size_t is,
                                                                                               const uint8_t* base_skip, uint32_t* n_deferred) {
     constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
     constexpr unsigned A = SH.a, L = A * H;
     static_assert(L <= 9 * 32 && H <= MSM_COMB_MAX_TEETH, "the recoded scalar is kept in nine words");
-    constexpr unsigned PER = TOP ? (256 / (SH.top_g ? SH.top_g : 1)) * (SH.top_g ? SH.top_g : 1) : 256;
-    const size_t m = m0 + blockIdx.y, i = (size_t)blockIdx.x * PER + threadIdx.x;  // (a grid row per MSM: no division per lane)
-    const bool live = threadIdx.x < PER && i < n;
-    if (blockIdx.x == 0 && threadIdx.x == 0) n_deferred[m] = 0;
+    constexpr unsigned GRP = TOP && SH.top_g ? SH.top_g : 1;
+    const unsigned span = 256u >> tsh, per = (span / GRP) * GRP;  // scalars per MSM of the workgroup: whole groups
+    const unsigned ml = threadIdx.x & ((1u << tsh) - 1u), il = threadIdx.x >> tsh;
+    const size_t m = m0 + ((size_t)blockIdx.y << tsh) + ml, i = (size_t)blockIdx.x * per + il;  // (no division per lane)
+    const bool live = il < per && i < n && m < m_end;
+    if (blockIdx.x == 0 && il == 0 && m < m_end) n_deferred[m] = 0;
     int code = 0;
     if (live) {
         const bool skip = base_skip[i] != 0;
@@ -315,7 +329,10 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
             }
         }
         w[(L - 1) >> 5] |= 1u << ((L - 1) & 31);
-        uint32_t* out = digits + (m * A) * nd + i;
+        uint32_t* out = digits + (m * A) * rs + i * is;
+        constexpr bool VEC = A % 4 == 0 && A <= 32;  // (more columns than that: a toy comb, word stores)
+        const bool vec = VEC && tsh != 0;  // (the launcher gives tsh != 0 to the item-major layout alone)
+        uint32_t dv[VEC ? A : 1];
         // Column j's index is the bits j + A k of t.  Shifted right by (A - 1) k + c0, tooth k's bits of the C columns from c0 on sit at
         // k + (j - c0): one shift per tooth and chunk of columns, and the teeth k, k + C, .. land in disjoint windows [k, k + C) that
         // are merged before the columns take their bits — diag[j - c0] = idx_j << (j - c0), from one AND-OR per column and C teeth.
@@ -325,7 +342,14 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
             const uint32_t top = idx >> (H - 1), mask = (1u << (H - 1)) - 1u;
             const uint32_t low = top ? (idx & mask) : (~idx & mask);  // top tooth -1: minus the entry of the complemented teeth
             const uint32_t neg = (top ? 0u : 1u) ^ (even ? 1u : 0u);
-            out[(size_t)j * nd] = low | (neg << 31);
+            const uint32_t d = low | (neg << 31);
+            if constexpr (VEC) {
+                if (vec) {
+                    dv[j] = skip ? MSM_COMB_SKIP : d;
+                    return;
+                }
+            }
+            out[(size_t)j * rs] = d;
         };
         if constexpr (H < 6) {
 #pragma unroll
@@ -360,26 +384,32 @@ template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_
                 for (unsigned j = c0; j < c0 + C && j < A; j++) emit(j, diag[j - c0] >> (j - c0));
             }
         }
-        if (skip) {  // (written over afterwards, by the lanes concerned alone: nothing per column for the others)
+        if constexpr (VEC) {
+            if (vec) {
+#pragma unroll
+                for (unsigned j = 0; j < A; j += 4) *reinterpret_cast<MsmCombDigit4*>(out + j) = MsmCombDigit4{{dv[j], dv[j + 1], dv[j + 2], dv[j + 3]}};
+            }
+        }
+        if (skip && !vec) {  // (written over afterwards, by the lanes concerned alone: nothing per column for the others)
 #pragma unroll 1
-            for (unsigned j = 0; j < A; j++) out[(size_t)j * nd] = MSM_COMB_SKIP;
+            for (unsigned j = 0; j < A; j++) out[(size_t)j * rs] = MSM_COMB_SKIP;
         }
     }
     if constexpr (TOP) {
         constexpr unsigned G = SH.top_g, B = SH.top_b;
         __shared__ int codes[256];
-        codes[threadIdx.x] = code;
+        codes[ml * span + il] = code;  // (the codes of one MSM side by side)
         __syncthreads();
-        const size_t grp = (size_t)blockIdx.x * (PER / G) + threadIdx.x, nv = msm_comb_virtual(n, SH);
-        if (threadIdx.x < PER / G && grp < nv * A) {
+        const size_t grp = (size_t)blockIdx.x * (per / G) + il, nv = msm_comb_virtual(n, SH);
+        if (il < per / G && grp < nv * A && m < m_end) {
             uint32_t idx = 0, pw = 1;
 #pragma unroll
             for (unsigned pos = 0; pos < G; pos++) {
-                idx += (uint32_t)(codes[threadIdx.x * G + pos] + (int)((B - 1) / 2)) * pw;
+                idx += (uint32_t)(codes[ml * span + il * G + pos] + (int)((B - 1) / 2)) * pw;
                 pw *= B;
             }
             const size_t v = grp / A, j = grp - v * A;
-            digits[(m * A + j) * nd + n + v] = idx == (SH.top_entries - 1) / 2 ? MSM_COMB_SKIP : (uint32_t)((v * (A - 1) + j) << (H - 1)) + idx;  // (B^g - 1) / 2: every code zero
+            digits[(m * A + j) * rs + (n + v) * is] = idx == (SH.top_entries - 1) / 2 ? MSM_COMB_SKIP : (uint32_t)((v * (A - 1) + j) << (H - 1)) + idx;  // (B^g - 1) / 2: every code zero
         }
     }
 }
@@ -506,6 +536,85 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_kernel(cons
     if (tid < a) partial[((size_t)m * G + g) * a + tid] = red[tid * pl.q];
 }
 
+// The ROW WALK: the same accumulation with lanes bound to ROWS — row = m a + j, one (MSM, column) pair, R = M a of them in a
+// launch — where msm_comb_kernel binds q lanes to a column of ONE MSM.  A workgroup takes MSM_BLOCK consecutive rows (they need not
+// be whole MSMs; rows from R up do nothing) and one chunk [i0, i1) of the n scalars, chunk c = blockIdx.x / W of G chunks of
+// ceil(n / G) scalars (the last ones may be short or empty), W = ceil(R / MSM_BLOCK).  At step i every lane adds its row's entry of
+// scalar i: the block msm_comb_block_of(i) and is_virtual are wave-uniform, so all lanes of a workgroup — and all workgroups of a
+// chunk — read ONE base's block of 2^(h-1) entries per step (G blocks on the chip at a time, against q per workgroup and phase of
+// msm_comb_kernel: address-translation reach).  digits: item-major, digits[i R + row] — a wave's load is 256 contiguous bytes.
+// A lane's sum IS its row's share of the chunk: no LDS, no barrier, no tree, no left-over lanes; it is stored chunk-major,
+// partial[c R + row], and msm_comb_rowsum_kernel adds the G chunks of a row.
+template <bool NARROW>
+__global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_rows_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits,
+                                                                                  unsigned n, unsigned R, unsigned W, unsigned G, G1Xyzz* partial,
+                                                                                  MsmDeferred* deferred, size_t deferred_stride, uint32_t* n_deferred,
+                                                                                  unsigned n_real, unsigned top_delta) {
+    const unsigned c = blockIdx.x / W, row = (blockIdx.x - c * W) * MSM_BLOCK + threadIdx.x;
+    if (row >= R) return;
+    const unsigned per = (n + G - 1) / G;
+    const unsigned i0 = c * per < n ? c * per : n, i1 = i0 + per < n ? i0 + per : n;
+    const unsigned m = row / a, j = row - m * a;
+    const uint32_t* dg = digits + row;
+    G1XyzzL run = g1l_identity();
+    if (i0 < i1) {
+        // Two steps deep: the entry of step i + 1 and the digit of step i + 2 are requested before the addition of step i, so both
+        // latencies pass under its ~2 100 instructions.  (The workgroups of a round of the chip's slots start together and run in lock
+        // step: without this the four waves of a SIMD wait for their entries together — VALU busy 0.86 with no translation miss
+        // left.  The kernel has the registers for it: 86 without the second entry.)  A skipped item requests entry 0 of its block
+        // and the steps past the chunk's end request the last item again: valid addresses, no branch around the loads.
+        const unsigned last = i1 - 1;
+        const auto entry = [&](unsigned i, uint32_t d) PLONK_LAMBDA_INLINE {
+            const uint32_t blk = i + (i >= n_real ? top_delta : 0u), e = d == MSM_COMB_SKIP ? 0u : d & 0x7fffffffu;
+            if constexpr (NARROW) return lookup + ((blk << hb) + e);
+            else return lookup + (((size_t)blk << hb) + e);
+        };
+        uint32_t d = dg[(size_t)i0 * R], dn = dg[(size_t)(i0 < last ? i0 + 1 : last) * R];
+        const G1Affine* src = entry(i0, d);
+        Fq x = fp_load(&src->x), y = fp_load(&src->y);
+        for (unsigned i = i0; i < i1; i++) {
+            const unsigned in = i < last ? i + 1 : last, in2 = i + 2 < last ? i + 2 : last;
+            const uint32_t dn2 = dg[(size_t)in2 * R];
+            const G1Affine* sn = entry(in, dn);
+            const Fq xn = fp_load(&sn->x), yn = fp_load(&sn->y);
+            if (d != MSM_COMB_SKIP) {  // (an identity entry is known by its digit: no test of the entry itself)
+                bool add = true;  // (a joint entry can be the identity under non-zero codes: msm_comb_kernel)
+                if (i >= n_real) add = !(fp_is_zero(x) && fp_is_zero(y));
+                if (add && !g1l_madd_signed(run, x, y, (uint32_t)((int32_t)d >> 31))) {  // equal or opposite: see msm_accumulate_kernel
+                    const uint32_t sl = atomicAdd(n_deferred + m, 1u);
+                    if (sl < MSM_DEFER_CAP) deferred[(size_t)m * deferred_stride + sl] = MsmDeferred{(uint32_t)(j * n + i), d};
+                }
+            }
+            d = dn;
+            dn = dn2;
+            x = xn;
+            y = yn;
+        }
+    }
+    partial[(size_t)c * R + row] = g1l_to_piece(run);
+}
+
+// colsum[row] = sum_c partial[c R + row], the G chunks of the row walk.  MSM_ROWSUM_LANES = 4 lanes per row take the chunks c = l
+// (mod 4) serially and two butterfly steps join them: 4 (ceil(G / 4) + 2) general additions per row where a wave per row
+// (msm_comb_colsum_kernel) spends 64 x 7 — 3.9 % of the accumulation's VALU instructions at the rule's G = 42 and 64 (1.8 % at G = 14),
+// against a quarter.  ONE lane per row would be the least work (G additions), but its chain of G serial additions in R / 64 waves took
+// 157 us per launch of 1 152 MSMs at G = 14 and a twelfth of the chip's issue slots, on a queue whose next kernel waits for it.  The layout is what msm_comb_finalize_kernel
+// reads with G = 1.
+#define MSM_ROWSUM_LANES 4
+__global__ void __launch_bounds__(64) msm_comb_rowsum_kernel(const G1Xyzz* partial, unsigned G, unsigned R, unsigned a, G1Xyzz* colsum, uint32_t* n_deferred) {
+    const unsigned lane = threadIdx.x, row = blockIdx.x * (64 / MSM_ROWSUM_LANES) + lane / MSM_ROWSUM_LANES, l = lane % MSM_ROWSUM_LANES;
+    G1XyzzL acc = g1l_identity();  // (a lane past the last row keeps the identity: every lane takes part in the exchanges)
+    bool ok = true;
+    if (row < R) {
+#pragma unroll 1
+        for (unsigned c = l; c < G; c += MSM_ROWSUM_LANES) ok &= g1l_add_fast(acc, g1l_from_piece(&partial[(size_t)c * R + row]));
+    }
+    ok &= g1l_wave_reduce_step<1>(acc, lane);
+    ok &= g1l_wave_reduce_step<2>(acc, lane);
+    if (!ok && row < R) atomicOr(n_deferred + row / a, MSM_COMB_REDO);  // equal or opposite operands somewhere: msm_comb_slow_kernel
+    if (l == 0 && row < R) colsum[row] = g1l_to_piece_wide(acc);
+}
+
 // colsum[m * a + j] = sum_g partial[(m * G + g) * a + j]: a wave per (MSM, column), lane g (G <= 64)
 __global__ void __launch_bounds__(64) msm_comb_colsum_kernel(const G1Xyzz* partial, unsigned G, unsigned a, G1Xyzz* colsum, uint32_t* n_deferred) {
     const size_t m = blockIdx.x / a, j = blockIdx.x % a;
@@ -572,19 +681,21 @@ template <unsigned LPM> __global__ void __launch_bounds__(64) msm_comb_finalize_
 
 // Recovery path (MSM_DEFER_CAP): MSM m recomputed from its digits with the general formulas; one workgroup per MSM, which exits
 // at once unless the MSM overflowed its deferred list.  Lane t: Horner over the columns of the scalars t, t + 256, ..
-__global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits, size_t n,
-                                                            const uint32_t* n_deferred, Fq* out_xy, uint8_t* flags, unsigned n_real, unsigned top_delta) {
+// (rs, is): the digits' row and item strides (msm_comb_digits_kernel).
+__global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits, size_t n, size_t rs,
+                                                            size_t is, const uint32_t* n_deferred, Fq* out_xy, uint8_t* flags, unsigned n_real,
+                                                            unsigned top_delta) {
     __shared__ G1Xyzz red[256];
     const unsigned m = blockIdx.x, tid = threadIdx.x;
     if (!msm_comb_needs_redo(n_deferred[m])) return;
-    const uint32_t* dg = digits + (size_t)m * a * n;
+    const uint32_t* dg = digits + (size_t)m * a * rs;
     G1Xyzz acc = g1_xyzz_identity();
 #pragma unroll 1
     for (int j = (int)a - 1; j >= 0; j--) {
         g1_dbl(acc);
 #pragma unroll 1
         for (size_t i = tid; i < n; i += 256) {
-            const uint32_t d = dg[(size_t)j * n + i];
+            const uint32_t d = dg[(size_t)j * rs + i * is];
             if (d == MSM_COMB_SKIP) continue;
             const G1Affine* src = lookup + ((msm_comb_block_of(i, n_real, top_delta) << hb) + (d & 0x7fffffffu));
             G1Affine pt;
@@ -784,25 +895,27 @@ static void msm_comb_verify(plonk_ctx* ctx, const plonk_srs* srs, const MsmLooku
 // digits kernel of the comb with h teeth (one instantiation per tooth count: the bit gather is unrolled at compile time); TOP: the
 // comb with top tables, whose workgroups take whole groups of scalars and add the virtual scalars' digits (nd = n + their number)
 template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ctx, const Fr* d_scalars, size_t n, size_t stride, size_t inner,
-                                                                   size_t outer_stride, size_t M, uint32_t* digits, size_t nd, const uint8_t* base_skip,
-                                                                   uint32_t* n_deferred) {
+                                                                   size_t outer_stride, size_t M, uint32_t* digits, size_t nd, bool item_major,
+                                                                   const uint8_t* base_skip, uint32_t* n_deferred) {
     if constexpr (!TOP || msm_comb_top_ok(H)) {
         constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
-        constexpr unsigned G = TOP ? SH.top_g : 1, PER = (256 / G) * G;
+        constexpr unsigned G = TOP ? SH.top_g : 1;
+        const size_t rs = item_major ? 1 : nd, is = item_major ? M * SH.a : 1;  // column-major digits[row][i] / item-major digits[i][row]
+        const unsigned tsh = item_major ? 2 : 0, PER = ((256u >> tsh) / G) * G;  // item-major: four MSMs per workgroup (the kernel's header)
         size_t gx = (n + PER - 1) / PER;
         if (TOP) {  // every virtual scalar's digit is written, also those of the groups past the last scalar
             const size_t gv = ((nd - n) * SH.a + PER / G - 1) / (PER / G);
             gx = gx > gv ? gx : gv;
         }
-        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, const uint8_t*, uint32_t*) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
-        for (size_t m0 = 0; m0 < M; m0 += 32768) {  // (a grid's second dimension ends at 65 535)
-            const size_t rows = M - m0 < 32768 ? M - m0 : 32768;
-            PLONK_LAUNCH(kern, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, ctx->stream, d_scalars, n, stride, inner,
-                         outer_stride, m0, digits, nd, base_skip, n_deferred);
+        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, size_t, unsigned, uint32_t*, size_t, size_t, size_t, const uint8_t*, uint32_t*) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
+        for (size_t m0 = 0; m0 < M; m0 += (size_t)32768 << tsh) {  // (a grid's second dimension ends at 65 535)
+            const size_t rows = M - m0 < ((size_t)32768 << tsh) ? M - m0 : (size_t)32768 << tsh;
+            PLONK_LAUNCH(kern, dim3((unsigned)gx, (unsigned)((rows + (1u << tsh) - 1) >> tsh)), dim3(256), 0, ctx->stream, d_scalars, n, stride, inner,
+                         outer_stride, m0, M, tsh, digits, nd, rs, is, base_skip, n_deferred);
         }
     }
 }
-typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, const uint8_t*, uint32_t*);
+typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, bool, const uint8_t*, uint32_t*);
 template <bool TOP, unsigned... H> static msm_comb_digits_fn msm_comb_digits_for(unsigned h, std::integer_sequence<unsigned, H...>) {
     msm_comb_digits_fn fn = nullptr;
     ((h == H + 2 && (!TOP || msm_comb_top_ok(H + 2)) ? (void)(fn = &msm_comb_launch_digits<H + 2, TOP>) : (void)0), ...);
@@ -820,11 +933,29 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     const unsigned top_delta = (unsigned)(srs->n_points - n_real);  // block of virtual scalar n_real + v = n_points + v (+ the digit's offset)
     PLONK_REQUIRE((uint64_t)n * a < ((uint64_t)1 << 32), PLONK_ERR_ARG, "MSM size %zu too large for the lookup path", n_real);
     PLONK_REQUIRE(msm_comb_top_reach_ok(n_real, sh), PLONK_ERR_ARG, "MSM size %zu too large for the top tables of %u teeth", n_real, h);
-    // enough waves to occupy 1024 SIMDs three to four deep, in as few workgroups per MSM as that takes; at least two additions per lane
-    unsigned G = msm_groups_per_msm(ctx, M, 64, 3072 / (MSM_BLOCK / 64), 0.035, n * a, 2);
-    while (G > 1 && (size_t)G > n) G /= 2;
+    // Which accumulation kernel.  The row walk (msm_comb_rows_kernel) launches W = ceil(R / 256) workgroups of rows times G chunks of
+    // scalars, THREE rounds of the chip's workgroup slots: G = 3 slots / W, lowered until a chunk holds 32 scalars (a chunk's flush
+    // and its addition in the row sum cost about 1.3 additions: under 4 %).  One round — every slot filled exactly once — is the
+    // least overhead and the slowest step: the launch then holds the whole chip for its length and lets go of it at once, so the
+    // other streams' kernels cannot fill in beside it (20 streams: 208.2 ms per step at one round, 204.6 at 1.5, 202.2 - 203.1 at
+    // two, 201.0 at three, against the column-lane kernel's 205.0 - 205.6; docs/HISTORY.md).  It is taken when W G fills half the
+    // slots; fewer MSMs — the latency paths — keep msm_comb_kernel, whose workgroups split ONE MSM.  ctx->msm_groups has no say here: it means workgroups
+    // per MSM, for msm_comb_kernel alone.  Test flags (plonk_msm_lookup_configure mode | 128, | 256) force either form; with the row
+    // walk forced a non-zero msm_groups is the chunk count, which makes several chunks reachable at toy sizes.
+    const size_t R = M * a, W = (R + MSM_BLOCK - 1) / MSM_BLOCK, slots = 4 * (size_t)device_cus(ctx->device);
+    size_t Gr = 3 * slots / W ? 3 * slots / W : 1;
+    if (Gr > n / 32) Gr = n / 32 ? n / 32 : 1;
+    bool rows = ctx->msm_comb_walk == 1 || (ctx->msm_comb_walk == 0 && W * Gr >= slots / 2);
+    if (ctx->msm_comb_walk == 1 && ctx->msm_groups) Gr = ctx->msm_groups < n ? ctx->msm_groups : n;
+    if (R > ((size_t)1 << 31) || W * Gr > ((size_t)1 << 31)) {
+        PLONK_REQUIRE(ctx->msm_comb_walk != 1, PLONK_ERR_ARG, "%zu MSMs are too many for the row walk", M);
+        rows = false;
+    }
+    // msm_comb_kernel: enough waves to occupy 1024 SIMDs three to four deep, in as few workgroups per MSM as that takes; at least two additions per lane
+    unsigned G = rows ? (unsigned)Gr : msm_groups_per_msm(ctx, M, 64, 3072 / (MSM_BLOCK / 64), 0.035, n * a, 2);
+    while (!rows && G > 1 && (size_t)G > n) G /= 2;
     MsmScratch s;
-    const size_t part_off = s.take(M * G * a * sizeof(G1Xyzz)), col_off = s.take(G >= 4 ? M * a * sizeof(G1Xyzz) : 0), cnt_off = s.take(M * 4);
+    const size_t part_off = s.take(M * G * a * sizeof(G1Xyzz)), col_off = s.take(rows || G >= 4 ? M * a * sizeof(G1Xyzz) : 0), cnt_off = s.take(M * 4);
     const size_t dfr_off = s.take(M * MSM_DEFER_CAP * sizeof(MsmDeferred)), dig_off = s.take(M * a * n * 4);
     PLONK_TRY(ctx_scratch(ctx, 1, s.total, (void**)&s.base));
     G1Xyzz *partial = s.at<G1Xyzz>(part_off), *colsum = s.at<G1Xyzz>(col_off);
@@ -834,19 +965,33 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     const msm_comb_digits_fn digits_fn = top ? msm_comb_digits_for<true>(h, teeth) : msm_comb_digits_for<false>(h, teeth);
     PLONK_REQUIRE(digits_fn, PLONK_ERR_ARG, "no comb of %u teeth", h);
     PLONK_TRY(prof_begin(ctx, "msm_digits", (double)M * (double)n * (32.0 + 4.0 * a)));
-    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n, srs->shared->base_skip, n_deferred);  // (also zeroes n_deferred)
+    // digits: column-major digits[row][i] for msm_comb_kernel, item-major digits[i][row] for the row walk
+    const size_t dig_rs = rows ? 1 : n, dig_is = rows ? R : 1;
+    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n, rows, srs->shared->base_skip, n_deferred);  // (also zeroes n_deferred)
     PLONK_TRY(prof_end(ctx));
     const size_t lds = (size_t)(MSM_BLOCK + a) * sizeof(G1Xyzz);
-    PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));
+    PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));  // (the accumulation, whichever kernel runs it)
     // every entry index fits 32 bits (and no test asked for the wide form: plonk_msm_lookup_configure mode | 64)
     const bool narrow = !ctx->msm_comb_wide && srs->shared->bytes / sizeof(G1Affine) <= ((uint64_t)1 << 32);
     const auto comb_kernel = narrow ? msm_comb_kernel<true> : msm_comb_kernel<false>;
-    PLONK_LAUNCH(comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a,
-                 (const uint32_t*)digits, n, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
+    const auto rows_kernel = narrow ? msm_comb_rows_kernel<true> : msm_comb_rows_kernel<false>;
+    if (rows)
+        PLONK_LAUNCH(rows_kernel, dim3((unsigned)(W * G)), dim3(MSM_BLOCK), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, (unsigned)n, (unsigned)R,
+                     (unsigned)W, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
+    else
+        PLONK_LAUNCH(comb_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), lds, ctx->stream, table, hb, a,
+                     (const uint32_t*)digits, n, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred, (unsigned)n_real, top_delta);
     PLONK_TRY(prof_end(ctx));
     const G1Xyzz* sums = partial;
     unsigned Gf = G;
-    if (G >= 4) {  // few MSMs in many pieces: a wave per (MSM, column) sums the pieces in parallel
+    if (rows) {  // four lanes per row sum its G chunks ("msm_comb_rowsum" is recorded by the row walk alone: how a test tells the forms apart)
+        PLONK_TRY(prof_begin(ctx, "msm_comb_rowsum", (double)R * (double)(G + 1) * sizeof(G1Xyzz)));
+        PLONK_LAUNCH(msm_comb_rowsum_kernel, dim3((unsigned)((R + 64 / MSM_ROWSUM_LANES - 1) / (64 / MSM_ROWSUM_LANES))), dim3(64), 0, ctx->stream, (const G1Xyzz*)partial, G, (unsigned)R, a, colsum,
+                     n_deferred);
+        PLONK_TRY(prof_end(ctx));
+        sums = colsum;
+        Gf = 1;
+    } else if (G >= 4) {  // few MSMs in many pieces: a wave per (MSM, column) sums the pieces in parallel
         PLONK_LAUNCH(msm_comb_colsum_kernel, dim3((unsigned)(M * a)), dim3(64), 0, ctx->stream, (const G1Xyzz*)partial, G, a, colsum, n_deferred);
         sums = colsum;
         Gf = 1;
@@ -860,8 +1005,8 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     if (M >= 64) PLONK_COMB_FINALIZE(4);
     else PLONK_COMB_FINALIZE(16);
 #undef PLONK_COMB_FINALIZE
-    PLONK_LAUNCH(msm_comb_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, n, (const uint32_t*)n_deferred,
-                 d_out_xy, d_flags, (unsigned)n_real, top_delta);
+    PLONK_LAUNCH(msm_comb_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, n, dig_rs, dig_is,
+                 (const uint32_t*)n_deferred, d_out_xy, d_flags, (unsigned)n_real, top_delta);
     PLONK_CHECK_HIP(hipGetLastError());
     return PLONK_OK;
 }
