@@ -457,12 +457,33 @@ int plonk_pairing_check(const uint8_t* g1_xy_le, const uint8_t* g1_is_identity, 
  *                           commitment is not on the curve, bit 2 = a commitment is the identity.  Such a proof has weight zero.
  *   plonk_verifier_fold     sums over the proofs lo <= i < hi with status 0: L and R as canonical x||y LE + identity flags.  Any
  *                           sub-range of a loaded batch can be folded; only range sums and the nine fixed-point products are redone.
- *   plonk_g1_mul_many       count products k_j * P_j: points x||y canonical LE ((0,0) = identity), scalars canonical LE32.       */
+ *   plonk_g1_mul_many       count products k_j * P_j: points x||y canonical LE ((0,0) = identity), scalars canonical LE32.
+ *
+ * A table of circuits of ONE setup (the same [x]_2: the caller's precondition, nothing here can test it).  Every proof's check
+ * is over the same [x]_2 whatever its circuit, so a batch mixed of the table's circuits folds under the same weights — index =
+ * the proof's position in the mixed batch — into one pairing check; only the eight key points a proof's fixed scalars multiply are
+ * its circuit's.  A table of one circuit gives the folds of plonk_verifier_create, byte for byte.
+ *   plonk_verifier_create_multi   n_circuits in 1 .. PLONK_VERIFIER_MAX_CIRCUITS (PLONK_ERR_ARG otherwise); log_n[c], n_public[c] and
+ *                           vk_xy_le[c][8 * 64] as plonk_verifier_create takes them, with the same tests.  The same handle type:
+ *                           status, fold and destroy as above.
+ *   plonk_verifier_load_multi     circuit[b] < n_circuits: the circuit of proof b (PLONK_ERR_ARG otherwise).  public_le32: the rows one
+ *                           after the other in proof order, row b of n_public[circuit[b]] values; n_public_values must be their
+ *                           sum (PLONK_ERR_ARG).
+ *   plonk_verifier_load_provers   the batch is every prover's resident batch, one after the other in list order, without a trip through
+ *                           the host; circuit[i] labels all of prover i's proofs.  PLONK_ERR_ARG: a prover whose (log_n, n_public) is
+ *                           not its labelled circuit's, or on another device; PLONK_ERR_STATE: a prover with no resident batch.
+ *   plonk_verifier_load, plonk_verifier_load_prover on a table of more than one circuit: PLONK_ERR_STATE.                        */
+#define PLONK_VERIFIER_MAX_CIRCUITS 64
 typedef struct plonk_verifier plonk_verifier;
 int plonk_verifier_create(plonk_ctx* ctx, unsigned log_n, const uint8_t vk_xy_le[8 * 64], size_t n_public, plonk_verifier** out);
 int plonk_verifier_destroy(plonk_verifier* v);
 int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs768, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]);
 int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch, const uint8_t seed[32]);
+int plonk_verifier_create_multi(plonk_ctx* ctx, size_t n_circuits, const unsigned* log_n, const uint8_t* vk_xy_le, const size_t* n_public,
+                                plonk_verifier** out);
+int plonk_verifier_load_multi(plonk_verifier* v, const uint8_t* proofs768, const uint32_t* circuit, const uint8_t* public_le32,
+                              size_t n_public_values, size_t batch, const uint8_t seed[32]);
+int plonk_verifier_load_provers(plonk_verifier* v, size_t n_provers, plonk_prover* const* provers, const uint32_t* circuit, const uint8_t seed[32]);
 int plonk_verifier_status(plonk_verifier* v, uint8_t* out_status);
 int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[64], uint8_t out_R[64], uint8_t out_is_identity[2]);
 int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_scalars_le32, size_t count, uint8_t* h_out_xy_le,

@@ -119,6 +119,9 @@ SIGNATURES = {
     "plonk_verifier_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "plonk_verifier_load": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t, _u8p]),
     "plonk_verifier_load_prover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, _u8p]),
+    "plonk_verifier_create_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), _u8p, ctypes.POINTER(ctypes.c_size_t), c_void_pp]),
+    "plonk_verifier_load_multi": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.POINTER(ctypes.c_uint32), _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p]),
+    "plonk_verifier_load_provers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp, ctypes.POINTER(ctypes.c_uint32), _u8p]),
     "plonk_verifier_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "plonk_verifier_fold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     "plonk_g1_mul_many": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]),

@@ -1,4 +1,5 @@
-// verifier.hip — the batch verifier (plonk_verifier_*, plonk_g1_mul_many): N proofs of one circuit, one pairing check.
+// verifier.hip — the batch verifier (plonk_verifier_*, plonk_g1_mul_many): N proofs of one circuit, or of a table of circuits
+// of one setup, under one pairing check.
 //
 // Reference behaviour replaced: verify_proof of TESTING_verifier_DO_NOT_OPEN.py:39-163 (challenges :266-277) for a batch.  Every
 // proof's check is e(L_i, [x]_2) == e(R_i, [1]_2) with L_i, R_i in G1, so with random 128-bit weights rho_i the batch is accepted
@@ -9,6 +10,8 @@
 //   g1_mul_many_kernel      one lane per (proof, term): k * P by double-and-add on the complete formulas of g1.h
 //   verify_fold_proof_kernel / verify_fold_kernel   L_i, R_i per proof (kept), then the sum over any range [lo, hi) + the nine
 //                           fixed-point products (their scalars are summed over the range in Fr first) -> two affine points
+// A table of K > 1 circuits folds with verify_fold_circuit_kernel (one workgroup per circuit: its eight key-point sums and
+// products -> one partial point) and verify_fold_multi_kernel (L, R over the range + the partials) in place of the last.
 #include <string.h>
 
 #include "plonk_internal.h"
@@ -80,15 +83,20 @@ PLONK_DEV void vf_store_xyzz(G1Xyzz* p, const G1Xyzz& r) {
 // transcript over its bytes as they are and its results are dropped (weight zero: identity points, zero scalars).
 //   init[0] = the transcript after Transcript(b"plonk"); init[1] = the weight transcript after the seed
 //   inv_tmp [B][max(n_public, 1)]: prefix products of the shared inversion (PI(zeta) and L0(zeta) need 1 / (zeta - w^i))
+// The domain and the number of public inputs are those of the proof's circuit: table[circuit[b]], public row at pub_off[b], inversion
+// row at inv_off[b] (exclusive sums of n_public and of max(n_public, 1) over the batch).  circuit == nullptr: every proof is of
+// table[0] and the rows are uniform, no offsets needed.  Only lane 0's tail, behind the last barrier, reads any of it, so the two
+// proofs of a workgroup may be of circuits of different size.
 struct VfShared {
     TcShared tc;
     uint32_t status;
     uint32_t pad_[3];
 };
-struct VfDomain { Fr w, w_inv, n_inv; unsigned log_n; };
-__global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint8_t* proofs, const Fr* pub, size_t n_public, size_t B,
-                                                                      const MerlinState* init, ChallengeConsts cc, VfDomain dom, Fr* inv_tmp,
-                                                                      G1Affine* pts, Fr* own, Fr* fixed, uint8_t* status) {
+struct VfCircuit { Fr w, w_inv, n_inv; uint32_t log_n, n_public; };
+__global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint8_t* proofs, const Fr* pub, size_t B, const MerlinState* init,
+                                                                      ChallengeConsts cc, const VfCircuit* table, const uint32_t* circuit,
+                                                                      const size_t* pub_off, const size_t* inv_off, Fr* inv_tmp, G1Affine* pts,
+                                                                      Fr* own, Fr* fixed, uint8_t* status) {
     __shared__ VfShared shared[2];
     const unsigned grp = threadIdx.x / TC_LANES, lane = threadIdx.x % TC_LANES;
     TcShared& sh = shared[grp].tc;
@@ -190,12 +198,17 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
         ev[e] = fp_to_mont(x);
     }
     const Fr a = ev[0], bb = ev[1], c = ev[2], s1 = ev[3], s2 = ev[4], zw = ev[5];
+    const VfCircuit* circ = table + (circuit ? circuit[b] : 0);
+    const Fr dom_w = fp_load(&circ->w), dom_w_inv = fp_load(&circ->w_inv), dom_n_inv = fp_load(&circ->n_inv);
+    const unsigned log_n = circ->log_n;
+    const size_t n_public = circ->n_public;
     Fr zn = zeta;
-    for (unsigned i = 0; i < dom.log_n; i++) zn = fp_sqr(zn);
+    for (unsigned i = 0; i < log_n; i++) zn = fp_sqr(zn);
     const Fr zh = fp_sub(zn, one);
     // 1 / (zeta - w^i), i < m, by ONE inversion (Montgomery's trick; a zero denominator inverts to zero, as the reference's field does)
     const size_t m = n_public ? n_public : 1;
-    Fr* tmp = inv_tmp + b * m;
+    Fr* tmp = inv_tmp + (circuit ? inv_off[b] : b * m);
+    const Fr* row = pub + (circuit ? pub_off[b] : b * n_public);
     Fr run = one, wi = one, w_last = one;
     for (size_t i = 0; i < m; i++) {
         Fr d = fp_sub(zeta, wi);
@@ -203,7 +216,7 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
         fp_store(tmp + i, run);
         run = fp_mul(run, d);
         w_last = wi;
-        wi = fp_mul(wi, dom.w);
+        wi = fp_mul(wi, dom_w);
     }
     Fr inv = fp_inv(run), sum = fp_zero<FrParams>(), inv0 = fp_zero<FrParams>();
     wi = w_last;
@@ -214,11 +227,11 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
             inv_i = fp_mul(inv, fp_load(tmp + i));
             inv = fp_mul(inv, d);
         }
-        if (i < n_public) sum = fp_add(sum, fp_mul(fp_mul(fp_load(pub + b * n_public + i), wi), inv_i));
+        if (i < n_public) sum = fp_add(sum, fp_mul(fp_mul(fp_load(row + i), wi), inv_i));
         if (i == 0) inv0 = inv_i;
-        wi = fp_mul(wi, dom.w_inv);
+        wi = fp_mul(wi, dom_w_inv);
     }
-    const Fr zhn = fp_mul(zh, dom.n_inv);
+    const Fr zhn = fp_mul(zh, dom_n_inv);
     const Fr pi = fp_neg(fp_mul(zhn, sum));  // PI = sum (-public_i) L_i(zeta), poly.py:181-195
     const Fr l0 = fp_mul(zhn, inv0);         // L0 = Z_H / (n (zeta - 1))
     const Fr bz = fp_mul(beta, zeta);
@@ -233,7 +246,7 @@ __global__ void __launch_bounds__(2 * TC_LANES) verify_scalars_kernel(const uint
     open = fp_add(open, fp_add(fp_mul(v5, s2), fp_mul(u, zw)));
     const Fr nzh = fp_neg(zh);
     const Fr s_own[VF_OWN] = {v, v2, v3, fp_add(fp_add(fp_mul(alpha, k1), l0a2), u), nzh, fp_mul(nzh, zn), fp_mul(nzh, fp_sqr(zn)),
-                              zeta, fp_mul(fp_mul(u, zeta), dom.w), one, u};
+                              zeta, fp_mul(fp_mul(u, zeta), dom_w), one, u};
     const Fr s_fix[VF_FIXED] = {fp_mul(a, bb), a, bb, c, one, v4, v5, fp_neg(fp_mul(ae12zw, beta)), fp_sub(r0, open)};
 #pragma unroll
     for (int k = 0; k < VF_OWN; k++) fp_store(o_own + k, fp_from_mont(fp_mul(s_own[k], rho)));
@@ -253,16 +266,22 @@ __global__ void __launch_bounds__(64) verify_fold_proof_kernel(const G1Xyzz* pro
     vf_store_xyzz(lr + j, acc);
 }
 
-// One workgroup: sum of L_b, of R_b and of the nine fixed-point scalars over lo <= b < hi (tree through LDS), the nine fixed-point
-// products, R += them, both sums to affine.  out_xy = L.x, L.y, R.x, R.y canonical; out_flags[side] = 1 for the identity.
 #define VF_FOLD_THREADS 256
-__global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_kernel(const G1Xyzz* lr, const Fr* fixed, const uint8_t* status, size_t lo, size_t hi,
-                                                                      const G1Affine* bases, Fq* out_xy, uint8_t* out_flags) {
-    __shared__ G1Xyzz red[VF_FOLD_THREADS];
-    __shared__ Fr fred[VF_FOLD_THREADS];
-    __shared__ G1Xyzz total[2];
-    __shared__ Fr fsum[VF_FIXED];
-    const unsigned tid = threadIdx.x;
+// red[0] = the sum of red[0 .. VF_FOLD_THREADS) (tree through LDS; every lane of the workgroup calls, the result is behind a barrier)
+PLONK_DEV void vf_tree_points(G1Xyzz* red, unsigned tid) {
+    __syncthreads();
+#pragma unroll 1
+    for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            G1Xyzz x = red[tid];
+            g1_add(x, red[tid + s]);
+            red[tid] = x;
+        }
+        __syncthreads();
+    }
+}
+// total[side] = the sum of lr[2 b + side] over the well-formed proofs lo <= b < hi, side = 0 (L), 1 (R)
+PLONK_DEV void vf_sum_lr(const G1Xyzz* lr, const uint8_t* status, size_t lo, size_t hi, G1Xyzz* red, G1Xyzz* total, unsigned tid) {
 #pragma unroll 1
     for (unsigned side = 0; side < 2; side++) {
         G1Xyzz acc = g1_xyzz_identity();
@@ -270,33 +289,51 @@ __global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_kernel(const G1Xy
         for (size_t b = lo + tid; b < hi; b += VF_FOLD_THREADS)
             if (!status[b]) g1_add(acc, vf_load_xyzz(lr + 2 * b + side));
         red[tid] = acc;
-        __syncthreads();
-#pragma unroll 1
-        for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
-            if (tid < s) {
-                G1Xyzz x = red[tid];
-                g1_add(x, red[tid + s]);
-                red[tid] = x;
-            }
-            __syncthreads();
-        }
+        vf_tree_points(red, tid);
         if (tid == 0) total[side] = red[0];
         __syncthreads();
     }
-#pragma unroll 1
-    for (unsigned k = 0; k < VF_FIXED; k++) {
-        Fr acc = fp_zero<FrParams>();
-        for (size_t b = lo + tid; b < hi; b += VF_FOLD_THREADS)
-            if (!status[b]) acc = fp_add(acc, fp_load(fixed + b * VF_FIXED + k));
-        fred[tid] = acc;
-        __syncthreads();
-        for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
-            if (tid < s) fred[tid] = fp_add(fred[tid], fred[tid + s]);
-            __syncthreads();
-        }
-        if (tid == 0) fsum[k] = fred[0];
+}
+// fsum[k] = the sum of fixed[b][k] over the well-formed proofs lo <= b < hi — of circuit `c` only, if `circuit` is given
+PLONK_DEV void vf_sum_fixed(const Fr* fixed, const uint8_t* status, const uint32_t* circuit, uint32_t c, size_t lo, size_t hi, unsigned k, Fr* fred,
+                            Fr* fsum, unsigned tid) {
+    Fr acc = fp_zero<FrParams>();
+    for (size_t b = lo + tid; b < hi; b += VF_FOLD_THREADS)
+        if (!status[b] && (!circuit || circuit[b] == c)) acc = fp_add(acc, fp_load(fixed + b * VF_FIXED + k));
+    fred[tid] = acc;
+    __syncthreads();
+    for (unsigned s = VF_FOLD_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) fred[tid] = fp_add(fred[tid], fred[tid + s]);
         __syncthreads();
     }
+    if (tid == 0) fsum[k] = fred[0];
+    __syncthreads();
+}
+// out_xy = L.x, L.y, R.x, R.y canonical; out_flags[side] = 1 for the identity.  Lanes 0 (L) and 1 (R); `extra` goes into R.
+PLONK_DEV void vf_fold_out(const G1Xyzz* total, const G1Xyzz* extra, unsigned n_extra, Fq* out_xy, uint8_t* out_flags, unsigned tid) {
+    if (tid >= 2) return;
+    G1Xyzz acc = total[tid];
+    if (tid == 1)
+#pragma unroll 1
+        for (unsigned k = 0; k < n_extra; k++) g1_add(acc, extra[k]);
+    const G1Affine r = g1_to_affine(acc);
+    fp_store(out_xy + 2 * tid, fp_from_mont(r.x));
+    fp_store(out_xy + 2 * tid + 1, fp_from_mont(r.y));
+    out_flags[tid] = g1_is_identity(acc) ? 1 : 0;
+}
+
+// One circuit.  One workgroup: sum of L_b, of R_b and of the nine fixed-point scalars over lo <= b < hi (tree through LDS), the nine
+// fixed-point products, R += them, both sums to affine.
+__global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_kernel(const G1Xyzz* lr, const Fr* fixed, const uint8_t* status, size_t lo, size_t hi,
+                                                                      const G1Affine* bases, Fq* out_xy, uint8_t* out_flags) {
+    __shared__ G1Xyzz red[VF_FOLD_THREADS];
+    __shared__ Fr fred[VF_FOLD_THREADS];
+    __shared__ G1Xyzz total[2];
+    __shared__ Fr fsum[VF_FIXED];
+    const unsigned tid = threadIdx.x;
+    vf_sum_lr(lr, status, lo, hi, red, total, tid);
+#pragma unroll 1
+    for (unsigned k = 0; k < VF_FIXED; k++) vf_sum_fixed(fixed, status, nullptr, 0, lo, hi, k, fred, fsum, tid);
     if (tid < VF_FIXED) {
         G1Affine p;
         p.x = fp_load(&bases[tid].x);
@@ -304,16 +341,48 @@ __global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_kernel(const G1Xy
         red[tid] = g1_mul_affine(p, fp_from_mont(fsum[tid]));
     }
     __syncthreads();
-    if (tid < 2) {
-        G1Xyzz acc = total[tid];
-        if (tid == 1)
+    vf_fold_out(total, red, VF_FIXED, out_xy, out_flags, tid);
+}
+
+// A table of K circuits, workgroup c = circuit c: the eight key-point scalars summed over the well-formed proofs OF CIRCUIT c in
+// lo <= b < hi, times bases[8 c + k], summed -> partial[c] (the identity if the range holds no such proof: every sum is zero).
+// The ninth scalar multiplies G1 whatever the circuit: workgroup 0 sums it over the whole range, partial[K] = that product.
+__global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_circuit_kernel(const Fr* fixed, const uint8_t* status, const uint32_t* circuit, size_t lo,
+                                                                              size_t hi, const G1Affine* bases, unsigned K, G1Xyzz* partial) {
+    __shared__ Fr fred[VF_FOLD_THREADS];
+    __shared__ Fr fsum[VF_FIXED];
+    __shared__ G1Xyzz prod[VF_FIXED];
+    const unsigned tid = threadIdx.x, c = blockIdx.x;
+    const unsigned terms = c == 0 ? VF_FIXED : VF_FIXED - 1;  // uniform over the workgroup
 #pragma unroll 1
-            for (unsigned k = 0; k < VF_FIXED; k++) g1_add(acc, red[k]);
-        const G1Affine r = g1_to_affine(acc);
-        fp_store(out_xy + 2 * tid, fp_from_mont(r.x));
-        fp_store(out_xy + 2 * tid + 1, fp_from_mont(r.y));
-        out_flags[tid] = g1_is_identity(acc) ? 1 : 0;
+    for (unsigned k = 0; k < terms; k++) vf_sum_fixed(fixed, status, k < VF_FIXED - 1 ? circuit : nullptr, c, lo, hi, k, fred, fsum, tid);
+    if (tid < terms) {
+        const G1Affine* base = tid < VF_FIXED - 1 ? bases + (size_t)c * (VF_FIXED - 1) + tid : bases + (size_t)K * (VF_FIXED - 1);
+        G1Affine p;
+        p.x = fp_load(&base->x);
+        p.y = fp_load(&base->y);
+        prod[tid] = g1_mul_affine(p, fp_from_mont(fsum[tid]));
     }
+    __syncthreads();
+    if (tid == 0) {
+        G1Xyzz acc = prod[0];
+#pragma unroll 1
+        for (unsigned k = 1; k < VF_FIXED - 1; k++) g1_add(acc, prod[k]);
+        vf_store_xyzz(partial + c, acc);
+        if (terms == VF_FIXED) vf_store_xyzz(partial + K, prod[VF_FIXED - 1]);
+    }
+}
+
+// ... and one workgroup after them: sum of L_b and of R_b over lo <= b < hi, R += the n_partial <= VF_FOLD_THREADS partial points
+__global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_multi_kernel(const G1Xyzz* lr, const uint8_t* status, size_t lo, size_t hi,
+                                                                            const G1Xyzz* partial, unsigned n_partial, Fq* out_xy, uint8_t* out_flags) {
+    __shared__ G1Xyzz red[VF_FOLD_THREADS];
+    __shared__ G1Xyzz total[2];
+    const unsigned tid = threadIdx.x;
+    vf_sum_lr(lr, status, lo, hi, red, total, tid);
+    red[tid] = tid < n_partial ? vf_load_xyzz(partial + tid) : g1_xyzz_identity();
+    vf_tree_points(red, tid);
+    vf_fold_out(total, red, 1, out_xy, out_flags, tid);
 }
 
 // plonk_g1_mul_many's marshalling: canonical points -> Montgomery form with the range / curve tests, products -> canonical affine
@@ -346,19 +415,26 @@ __global__ void g1_mul_many_out_kernel(const G1Xyzz* prod, size_t count, Fq* out
 
 // ================================================================================================
 // host side
+static_assert(PLONK_VERIFIER_MAX_CIRCUITS + 1 <= VF_FOLD_THREADS, "verify_fold_multi_kernel: one lane per partial point");
+
 struct plonk_verifier {
     plonk_ctx* ctx;
-    unsigned log_n;
-    size_t n_public;
-    VfDomain dom;
+    unsigned n_circuits;     // K
+    VfCircuit* h_circ;       // [K] domain and number of public inputs of each circuit
+    VfCircuit* d_circ;
     ChallengeConsts chal;
     MerlinState h_init[2];   // [0] Transcript(b"plonk"), [1] the weight transcript after the seed of the last load
     MerlinState* d_init;
-    G1Affine* d_bases;       // [9] Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1 (Montgomery)
-    size_t cap, batch;       // allocated / loaded proofs
+    G1Affine* d_bases;       // [8 K + 1] Qm, Ql, Qr, Qo, Qc, S1, S2, S3 of every circuit, then G1 (Montgomery)
+    G1Xyzz* d_partial;       // [K + 1] verify_fold_circuit_kernel's points
+    size_t cap, cap_pub, cap_inv, batch;  // allocated proofs / public values / inversion values; loaded proofs
     uint8_t* d_proofs;       // [B][PROOF_BYTES]
-    Fr* d_pub;               // [B][n_public] Montgomery
+    Fr* d_pub;               // [B][n_public of the proof's circuit] Montgomery
     Fr* d_inv_tmp;           // [B][max(n_public, 1)]
+    size_t* d_off;           // [2][B] each proof's row in d_pub and in d_inv_tmp  } of a batch loaded with circuit labels:
+    uint32_t* d_circuit;     // [B] each proof's circuit                           } h_meta holds the three as they are uploaded
+    void* h_meta;
+    size_t h_meta_cap;
     G1Affine* d_pts;         // [B][11]
     Fr* d_own;               // [B][11] canonical
     Fr* d_fixed;             // [B][9] Montgomery
@@ -366,23 +442,29 @@ struct plonk_verifier {
     G1Xyzz* d_lr;            // [B][2]  L_b, R_b: any sub-range folds again from these
     uint8_t* d_status;       // [B]
     Fq* d_out;               // [4] + 2 flag bytes behind them
-    hipEvent_t ev;           // the prover's pack is done (plonk_verifier_load_prover)
+    hipEvent_t* evs;         // [n_evs] a prover's pack is done (plonk_verifier_load_prover, _load_provers: one per prover)
+    size_t n_evs;
 };
 
 static void verifier_free_batch(plonk_verifier* v) {
-    dev_free_all({(void**)&v->d_proofs, (void**)&v->d_pub, (void**)&v->d_inv_tmp, (void**)&v->d_pts, (void**)&v->d_own, (void**)&v->d_fixed,
-                  (void**)&v->d_prod, (void**)&v->d_lr, (void**)&v->d_status});
-    v->cap = v->batch = 0;
+    dev_free_all({(void**)&v->d_proofs, (void**)&v->d_pub, (void**)&v->d_inv_tmp, (void**)&v->d_off, (void**)&v->d_circuit, (void**)&v->d_pts,
+                  (void**)&v->d_own, (void**)&v->d_fixed, (void**)&v->d_prod, (void**)&v->d_lr, (void**)&v->d_status});
+    v->cap = v->cap_pub = v->cap_inv = v->batch = 0;
 }
 
-static int verifier_ensure(plonk_verifier* v, size_t B) {
-    if (B <= v->cap) return PLONK_OK;
+// room for B proofs with n_pub public values and n_inv inversion values in all
+static int verifier_ensure(plonk_verifier* v, size_t B, size_t n_pub, size_t n_inv) {
+    if (B <= v->cap && n_pub <= v->cap_pub && n_inv <= v->cap_inv) return PLONK_OK;
     PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));
+    B = B > v->cap ? B : v->cap;
+    n_pub = n_pub > v->cap_pub ? n_pub : v->cap_pub;
+    n_inv = n_inv > v->cap_inv ? n_inv : v->cap_inv;
     verifier_free_batch(v);
-    const size_t m = v->n_public ? v->n_public : 1;
     PLONK_TRY(dev_alloc((void**)&v->d_proofs, B * PROOF_BYTES));
-    PLONK_TRY(dev_alloc((void**)&v->d_pub, B * m * sizeof(Fr)));
-    PLONK_TRY(dev_alloc((void**)&v->d_inv_tmp, B * m * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_pub, n_pub * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_inv_tmp, n_inv * sizeof(Fr)));
+    PLONK_TRY(dev_alloc((void**)&v->d_off, 2 * B * sizeof(size_t)));
+    PLONK_TRY(dev_alloc((void**)&v->d_circuit, B * sizeof(uint32_t)));
     PLONK_TRY(dev_alloc((void**)&v->d_pts, B * VF_OWN * sizeof(G1Affine)));
     PLONK_TRY(dev_alloc((void**)&v->d_own, B * VF_OWN * sizeof(Fr)));
     PLONK_TRY(dev_alloc((void**)&v->d_fixed, B * VF_FIXED * sizeof(Fr)));
@@ -390,18 +472,56 @@ static int verifier_ensure(plonk_verifier* v, size_t B) {
     PLONK_TRY(dev_alloc((void**)&v->d_lr, B * 2 * sizeof(G1Xyzz)));
     PLONK_TRY(dev_alloc((void**)&v->d_status, B));
     v->cap = B;
+    v->cap_pub = n_pub;
+    v->cap_inv = n_inv;
     return PLONK_OK;
 }
 
-// the proofs and public inputs of `B` proofs are in place on the verifier's stream: weights, scalars, products, L_b and R_b
-static int verifier_run(plonk_verifier* v, size_t B, const uint8_t seed[32]) {
+// Host staging of a labelled batch: pub_off[B], inv_off[B] (size_t), circuit[B] (uint32_t), in the order they lie in h_meta
+struct VfMeta { size_t *pub_off, *inv_off; uint32_t* circuit; };
+static int verifier_meta(plonk_verifier* v, size_t B, VfMeta* m) {
+    const size_t bytes = B * (2 * sizeof(size_t) + sizeof(uint32_t));
+    if (bytes > v->h_meta_cap) {
+        PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));  // an upload from the old block may be on its way
+        free(v->h_meta);
+        v->h_meta_cap = 0;
+        v->h_meta = malloc(bytes);
+        PLONK_REQUIRE(v->h_meta, PLONK_ERR_NOMEM, "malloc(%zu) failed", bytes);
+        v->h_meta_cap = bytes;
+    }
+    m->pub_off = (size_t*)v->h_meta;
+    m->inv_off = m->pub_off + B;
+    m->circuit = (uint32_t*)(m->inv_off + B);
+    return PLONK_OK;
+}
+// proof b of the staging is of circuit c: its label and its rows; *n_pub and *n_inv run along
+static void verifier_meta_set(const plonk_verifier* v, const VfMeta& m, size_t b, uint32_t c, size_t* n_pub, size_t* n_inv) {
+    const size_t l = v->h_circ[c].n_public;
+    m.circuit[b] = c;
+    m.pub_off[b] = *n_pub;
+    m.inv_off[b] = *n_inv;
+    *n_pub += l;
+    *n_inv += l ? l : 1;
+}
+static int verifier_meta_upload(plonk_verifier* v, size_t B, const VfMeta& m) {
+    hipStream_t s = v->ctx->stream;
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_off, m.pub_off, B * sizeof(size_t), hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_off + v->cap, m.inv_off, B * sizeof(size_t), hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_circuit, m.circuit, B * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    return PLONK_OK;
+}
+
+// the proofs and public inputs of `B` proofs are in place on the verifier's stream (`labelled`: and their circuits and rows):
+// weights, scalars, products, L_b and R_b
+static int verifier_run(plonk_verifier* v, size_t B, const uint8_t seed[32], bool labelled) {
     plonk_ctx* ctx = v->ctx;
     hipStream_t s = ctx->stream;
     merlin_init(v->h_init[1], (const uint8_t*)"plonk-batch-verify", 18);
     merlin_append_message(v->h_init[1], (const uint8_t*)"seed", 4, seed, 32);
     PLONK_CHECK_HIP(hipMemcpyAsync(v->d_init, v->h_init, sizeof v->h_init, hipMemcpyHostToDevice, s));
-    PLONK_LAUNCH(verify_scalars_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, s, (const uint8_t*)v->d_proofs, (const Fr*)v->d_pub,
-                 v->n_public, B, (const MerlinState*)v->d_init, v->chal, v->dom, v->d_inv_tmp, v->d_pts, v->d_own, v->d_fixed, v->d_status);
+    PLONK_LAUNCH(verify_scalars_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, s, (const uint8_t*)v->d_proofs, (const Fr*)v->d_pub, B,
+                 (const MerlinState*)v->d_init, v->chal, (const VfCircuit*)v->d_circ, labelled ? (const uint32_t*)v->d_circuit : (const uint32_t*)nullptr,
+                 (const size_t*)v->d_off, (const size_t*)(v->d_off + v->cap), v->d_inv_tmp, v->d_pts, v->d_own, v->d_fixed, v->d_status);
     const size_t count = B * VF_OWN;
     PLONK_LAUNCH(g1_mul_many_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, (const G1Affine*)v->d_pts, (const Fr*)v->d_own, count,
                  v->d_prod);
@@ -412,35 +532,77 @@ static int verifier_run(plonk_verifier* v, size_t B, const uint8_t seed[32]) {
     return PLONK_OK;
 }
 
-static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned log_n, const uint8_t* vk_xy_le, size_t n_public) {
+static int verifier_events(plonk_verifier* v, size_t n) {
+    if (n <= v->n_evs) return PLONK_OK;
+    hipEvent_t* evs = (hipEvent_t*)realloc(v->evs, n * sizeof(hipEvent_t));
+    PLONK_REQUIRE(evs, PLONK_ERR_NOMEM, "realloc(%zu) failed", n * sizeof(hipEvent_t));
+    v->evs = evs;
+    for (; v->n_evs < n; v->n_evs++) PLONK_CHECK_HIP(hipEventCreate(&v->evs[v->n_evs]));
+    return PLONK_OK;
+}
+
+static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned K, const unsigned* log_n, const uint8_t* vk_xy_le, const size_t* n_public) {
     v->ctx = ctx;
-    v->log_n = log_n;
-    v->n_public = n_public;
-    v->dom.log_n = log_n;
-    v->dom.w = host_root_of_unity(log_n, false);
-    v->dom.w_inv = host_root_of_unity(log_n, true);
-    v->dom.n_inv = fp_inv(host_fr_u64((uint64_t)1 << log_n));
+    v->n_circuits = K;
     v->chal = challenge_consts();
     merlin_init(v->h_init[0], (const uint8_t*)"plonk", 5);
     v->h_init[1] = v->h_init[0];
-    G1Affine bases[VF_FIXED];
-    for (int k = 0; k < 8; k++) {
-        const uint8_t* q = vk_xy_le + 64 * k;
-        PLONK_REQUIRE(le32_below_modulus(q, true) && le32_below_modulus(q + 32, true), PLONK_ERR_ARG, "verification key point %d: a coordinate is not below p", k);
-        Fq x, y;
-        memcpy(x.v, q, 32);
-        memcpy(y.v, q + 32, 32);
-        bases[k].x = fp_to_mont(x);
-        bases[k].y = fp_to_mont(y);
-        PLONK_REQUIRE(g1_affine_is_identity(bases[k]) || g1_affine_on_curve(bases[k].x, bases[k].y), PLONK_ERR_ARG, "verification key point %d is not on the curve", k);
+    v->h_circ = (VfCircuit*)calloc(K, sizeof(VfCircuit));
+    G1Affine* bases = (G1Affine*)calloc(8 * (size_t)K + 1, sizeof(G1Affine));
+    int rc = v->h_circ && bases ? PLONK_OK : PLONK_ERR_NOMEM;
+    if (rc != PLONK_OK) plonk_set_error("calloc failed for %u circuits", K);
+    for (unsigned c = 0; c < K && rc == PLONK_OK; c++) {
+        rc = [&]() -> int {
+            PLONK_REQUIRE(log_n[c] >= 1 && log_n[c] <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "circuit %u: group_order 2^%u out of range", c, log_n[c]);
+            PLONK_REQUIRE(n_public[c] <= ((size_t)1 << log_n[c]), PLONK_ERR_ARG, "circuit %u: more public inputs than rows", c);
+            VfCircuit& t = v->h_circ[c];
+            t.log_n = log_n[c];
+            t.n_public = (uint32_t)n_public[c];
+            t.w = host_root_of_unity(log_n[c], false);
+            t.w_inv = host_root_of_unity(log_n[c], true);
+            t.n_inv = fp_inv(host_fr_u64((uint64_t)1 << log_n[c]));
+            for (int k = 0; k < 8; k++) {
+                const uint8_t* q = vk_xy_le + 64 * (8 * (size_t)c + k);
+                G1Affine& base = bases[8 * (size_t)c + k];
+                PLONK_REQUIRE(le32_below_modulus(q, true) && le32_below_modulus(q + 32, true), PLONK_ERR_ARG, "circuit %u, verification key point %d: a coordinate is not below p", c, k);
+                Fq x, y;
+                memcpy(x.v, q, 32);
+                memcpy(y.v, q + 32, 32);
+                base.x = fp_to_mont(x);
+                base.y = fp_to_mont(y);
+                PLONK_REQUIRE(g1_affine_is_identity(base) || g1_affine_on_curve(base.x, base.y), PLONK_ERR_ARG, "circuit %u, verification key point %d is not on the curve", c, k);
+            }
+            return PLONK_OK;
+        }();
     }
-    bases[8].x = fp_one<FqParams>();  // G1 = (1, 2)
-    bases[8].y = fp_dbl(bases[8].x);
-    PLONK_TRY(dev_alloc((void**)&v->d_init, sizeof v->h_init));
-    PLONK_TRY(dev_alloc((void**)&v->d_bases, sizeof bases));
-    PLONK_TRY(dev_alloc((void**)&v->d_out, 4 * sizeof(Fq) + 16));
-    PLONK_CHECK_HIP(hipEventCreate(&v->ev));
-    PLONK_CHECK_HIP(hipMemcpy(v->d_bases, bases, sizeof bases, hipMemcpyHostToDevice));
+    if (rc == PLONK_OK) rc = [&]() -> int {
+        G1Affine& g = bases[8 * (size_t)K];
+        g.x = fp_one<FqParams>();  // G1 = (1, 2)
+        g.y = fp_dbl(g.x);
+        const size_t base_bytes = (8 * (size_t)K + 1) * sizeof(G1Affine);
+        PLONK_TRY(dev_alloc((void**)&v->d_init, sizeof v->h_init));
+        PLONK_TRY(dev_alloc((void**)&v->d_bases, base_bytes));
+        PLONK_TRY(dev_alloc((void**)&v->d_circ, K * sizeof(VfCircuit)));
+        PLONK_TRY(dev_alloc((void**)&v->d_partial, ((size_t)K + 1) * sizeof(G1Xyzz)));
+        PLONK_TRY(dev_alloc((void**)&v->d_out, 4 * sizeof(Fq) + 16));
+        PLONK_TRY(verifier_events(v, 1));
+        PLONK_CHECK_HIP(hipMemcpy(v->d_bases, bases, base_bytes, hipMemcpyHostToDevice));
+        PLONK_CHECK_HIP(hipMemcpy(v->d_circ, v->h_circ, K * sizeof(VfCircuit), hipMemcpyHostToDevice));
+        return PLONK_OK;
+    }();
+    free(bases);
+    return rc;
+}
+
+static int verifier_create(plonk_ctx* ctx, unsigned K, const unsigned* log_n, const uint8_t* vk_xy_le, const size_t* n_public, plonk_verifier** out) {
+    plonk_verifier* v = new plonk_verifier();
+    memset((void*)v, 0, sizeof *v);
+    const int rc = verifier_init(v, ctx, K, log_n, vk_xy_le, n_public);
+    if (rc != PLONK_OK) {
+        plonk_verifier_destroy(v);
+        return rc;
+    }
+    *out = v;
     return PLONK_OK;
 }
 
@@ -449,17 +611,16 @@ extern "C" {
 int plonk_verifier_create(plonk_ctx* ctx, unsigned log_n, const uint8_t vk_xy_le[8 * 64], size_t n_public, plonk_verifier** out) {
     PLONK_REQUIRE(ctx && vk_xy_le && out, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(ctx);
-    PLONK_REQUIRE(log_n >= 1 && log_n <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "group_order 2^%u out of range", log_n);
-    PLONK_REQUIRE(n_public <= ((size_t)1 << log_n), PLONK_ERR_ARG, "more public inputs than rows");
-    plonk_verifier* v = new plonk_verifier();
-    memset((void*)v, 0, sizeof *v);
-    const int rc = verifier_init(v, ctx, log_n, vk_xy_le, n_public);
-    if (rc != PLONK_OK) {
-        plonk_verifier_destroy(v);
-        return rc;
-    }
-    *out = v;
-    return PLONK_OK;
+    return verifier_create(ctx, 1, &log_n, vk_xy_le, &n_public, out);
+}
+
+int plonk_verifier_create_multi(plonk_ctx* ctx, size_t n_circuits, const unsigned* log_n, const uint8_t* vk_xy_le, const size_t* n_public,
+                                plonk_verifier** out) {
+    PLONK_REQUIRE(ctx && log_n && vk_xy_le && n_public && out, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(n_circuits >= 1 && n_circuits <= PLONK_VERIFIER_MAX_CIRCUITS, PLONK_ERR_ARG, "%zu circuits: a table holds 1 to %d", n_circuits,
+                  PLONK_VERIFIER_MAX_CIRCUITS);
+    PLONK_ENTER(ctx);
+    return verifier_create(ctx, (unsigned)n_circuits, log_n, vk_xy_le, n_public, out);
 }
 
 int plonk_verifier_destroy(plonk_verifier* v) {
@@ -469,38 +630,110 @@ int plonk_verifier_destroy(plonk_verifier* v) {
         hipStreamSynchronize(v->ctx->stream);
     }
     verifier_free_batch(v);
-    dev_free_all({(void**)&v->d_init, (void**)&v->d_bases, (void**)&v->d_out});
-    if (v->ev) hipEventDestroy(v->ev);
+    dev_free_all({(void**)&v->d_init, (void**)&v->d_bases, (void**)&v->d_circ, (void**)&v->d_partial, (void**)&v->d_out});
+    for (size_t i = 0; i < v->n_evs; i++) hipEventDestroy(v->evs[i]);
+    free(v->evs);
+    free(v->h_circ);
+    free(v->h_meta);
     delete v;
     return PLONK_OK;
 }
 
 int plonk_verifier_load(plonk_verifier* v, const uint8_t* proofs, const uint8_t* public_le32, size_t batch, const uint8_t seed[32]) {
-    PLONK_REQUIRE(v && proofs && batch && seed && (public_le32 || !v->n_public), PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v && proofs && batch && seed, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v->n_circuits == 1, PLONK_ERR_STATE, "a verifier of %u circuits loads with plonk_verifier_load_multi", v->n_circuits);
+    const size_t n_public = v->h_circ[0].n_public;
+    PLONK_REQUIRE(public_le32 || !n_public, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(v->ctx);
     v->batch = 0;  // until the new batch is in place
-    PLONK_TRY(verifier_ensure(v, batch));
-    if (v->n_public) PLONK_TRY(plonk_fr_upload(v->ctx, v->d_pub, public_le32, batch * v->n_public));  // a value not below r: PLONK_ERR_ARG
+    PLONK_TRY(verifier_ensure(v, batch, batch * n_public, batch * (n_public ? n_public : 1)));
+    if (n_public) PLONK_TRY(plonk_fr_upload(v->ctx, v->d_pub, public_le32, batch * n_public));  // a value not below r: PLONK_ERR_ARG
     PLONK_CHECK_HIP(hipMemcpyAsync(v->d_proofs, proofs, batch * PROOF_BYTES, hipMemcpyHostToDevice, v->ctx->stream));
-    return verifier_run(v, batch, seed);
+    return verifier_run(v, batch, seed, false);
+}
+
+int plonk_verifier_load_multi(plonk_verifier* v, const uint8_t* proofs, const uint32_t* circuit, const uint8_t* public_le32, size_t n_public_values,
+                              size_t batch, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && proofs && circuit && batch && seed, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(v->ctx);
+    v->batch = 0;
+    VfMeta m;
+    PLONK_TRY(verifier_meta(v, batch, &m));
+    size_t n_pub = 0, n_inv = 0;
+    for (size_t b = 0; b < batch; b++) {
+        PLONK_REQUIRE(circuit[b] < v->n_circuits, PLONK_ERR_ARG, "proof %zu: circuit %u of a table of %u", b, circuit[b], v->n_circuits);
+        verifier_meta_set(v, m, b, circuit[b], &n_pub, &n_inv);
+    }
+    PLONK_REQUIRE(n_public_values == n_pub, PLONK_ERR_ARG, "%zu public values, the circuits of the batch take %zu", n_public_values, n_pub);
+    PLONK_REQUIRE(public_le32 || !n_pub, PLONK_ERR_ARG, "bad argument");
+    PLONK_TRY(verifier_ensure(v, batch, n_pub, n_inv));
+    if (n_pub) PLONK_TRY(plonk_fr_upload(v->ctx, v->d_pub, public_le32, n_pub));  // a value not below r: PLONK_ERR_ARG
+    PLONK_CHECK_HIP(hipMemcpyAsync(v->d_proofs, proofs, batch * PROOF_BYTES, hipMemcpyHostToDevice, v->ctx->stream));
+    PLONK_TRY(verifier_meta_upload(v, batch, m));
+    return verifier_run(v, batch, seed, true);
 }
 
 int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch, const uint8_t seed[32]) {
     PLONK_REQUIRE(v && p && batch && seed, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v->n_circuits == 1, PLONK_ERR_STATE, "a verifier of %u circuits loads with plonk_verifier_load_provers", v->n_circuits);
+    const VfCircuit& c = v->h_circ[0];
     PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->circuit.ctx->device, v->ctx->device);
-    PLONK_REQUIRE(p->circuit.log_n == v->log_n && p->circuit.n_public == v->n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %zu)",
-                  p->circuit.log_n, p->circuit.n_public, v->log_n, v->n_public);
+    PLONK_REQUIRE(p->circuit.log_n == c.log_n && p->circuit.n_public == c.n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %u)",
+                  p->circuit.log_n, p->circuit.n_public, c.log_n, c.n_public);
     PLONK_REQUIRE(batch == p->intake.resident_b, PLONK_ERR_STATE, "verify: batch %zu, but %zu proofs are resident in the prover", batch, p->intake.resident_b);
     PLONK_ENTER(v->ctx);
     v->batch = 0;
-    PLONK_TRY(verifier_ensure(v, batch));
+    PLONK_TRY(verifier_ensure(v, batch, batch * c.n_public, batch * (c.n_public ? c.n_public : 1)));
     // on the prover's stream, behind its five rounds.  The PROVER's status bytes land in d_status and are discarded on purpose
     // (verify_scalars_kernel overwrites them): a proof its prover flagged is verified like any other, and rejected
-    PLONK_TRY(prover_pack_device(p, batch, 0, v->d_proofs, v->d_status, v->ev));
-    PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->ev, 0));
-    if (v->n_public)
-        PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->intake.pub, batch * v->n_public * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
-    return verifier_run(v, batch, seed);
+    PLONK_TRY(prover_pack_device(p, batch, 0, v->d_proofs, v->d_status, v->evs[0]));
+    PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->evs[0], 0));
+    if (c.n_public)
+        PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->intake.pub, batch * c.n_public * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
+    return verifier_run(v, batch, seed, false);
+}
+
+int plonk_verifier_load_provers(plonk_verifier* v, size_t n_provers, plonk_prover* const* provers, const uint32_t* circuit, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && n_provers && provers && circuit && seed, PLONK_ERR_ARG, "bad argument");
+    size_t batch = 0;
+    for (size_t i = 0; i < n_provers; i++) {
+        plonk_prover* p = provers[i];
+        PLONK_REQUIRE(p, PLONK_ERR_ARG, "prover %zu is null", i);
+        PLONK_REQUIRE(circuit[i] < v->n_circuits, PLONK_ERR_ARG, "prover %zu: circuit %u of a table of %u", i, circuit[i], v->n_circuits);
+        const VfCircuit& c = v->h_circ[circuit[i]];
+        PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "prover %zu lives on device %d, the verifier on %d", i, p->circuit.ctx->device, v->ctx->device);
+        PLONK_REQUIRE(p->circuit.log_n == c.log_n && p->circuit.n_public == c.n_public, PLONK_ERR_ARG,
+                      "prover %zu's circuit (2^%u rows, %zu public inputs) is not circuit %u of the table (2^%u, %u)", i, p->circuit.log_n, p->circuit.n_public,
+                      circuit[i], c.log_n, c.n_public);
+        PLONK_REQUIRE(p->intake.resident_b, PLONK_ERR_STATE, "prover %zu has no resident batch", i);
+        batch += p->intake.resident_b;
+    }
+    PLONK_ENTER(v->ctx);
+    v->batch = 0;
+    VfMeta m;
+    PLONK_TRY(verifier_meta(v, batch, &m));
+    size_t n_pub = 0, n_inv = 0, b = 0;
+    for (size_t i = 0; i < n_provers; i++)
+        for (size_t j = 0; j < provers[i]->intake.resident_b; j++) verifier_meta_set(v, m, b++, circuit[i], &n_pub, &n_inv);
+    PLONK_TRY(verifier_ensure(v, batch, n_pub, n_inv));
+    PLONK_TRY(verifier_events(v, n_provers));
+    // every prover packs its slice on its own stream, behind its five rounds (its status bytes are overwritten, as above)
+    b = 0;
+    for (size_t i = 0; i < n_provers; i++) {
+        PLONK_TRY(prover_pack_device(provers[i], provers[i]->intake.resident_b, 0, v->d_proofs + b * PROOF_BYTES, v->d_status + b, v->evs[i]));
+        b += provers[i]->intake.resident_b;
+    }
+    b = 0;
+    for (size_t i = 0; i < n_provers; i++) {
+        plonk_prover* p = provers[i];
+        PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->evs[i], 0));
+        if (p->circuit.n_public)
+            PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub + m.pub_off[b], p->intake.pub, p->intake.resident_b * p->circuit.n_public * sizeof(Fr), hipMemcpyDeviceToDevice,
+                                           v->ctx->stream));
+        b += p->intake.resident_b;
+    }
+    PLONK_TRY(verifier_meta_upload(v, batch, m));
+    return verifier_run(v, batch, seed, true);
 }
 
 int plonk_verifier_status(plonk_verifier* v, uint8_t* out_status) {
@@ -519,8 +752,16 @@ int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[6
     PLONK_ENTER(v->ctx);
     hipStream_t s = v->ctx->stream;
     uint8_t* d_flags = reinterpret_cast<uint8_t*>(v->d_out + 4);
-    PLONK_LAUNCH(verify_fold_kernel, dim3(1), dim3(VF_FOLD_THREADS), 0, s, (const G1Xyzz*)v->d_lr, (const Fr*)v->d_fixed, (const uint8_t*)v->d_status, lo, hi,
-                 (const G1Affine*)v->d_bases, v->d_out, d_flags);
+    const unsigned K = v->n_circuits;
+    if (K == 1) {  // every proof is of circuit 0, labelled or not
+        PLONK_LAUNCH(verify_fold_kernel, dim3(1), dim3(VF_FOLD_THREADS), 0, s, (const G1Xyzz*)v->d_lr, (const Fr*)v->d_fixed, (const uint8_t*)v->d_status, lo, hi,
+                     (const G1Affine*)v->d_bases, v->d_out, d_flags);
+    } else {
+        PLONK_LAUNCH(verify_fold_circuit_kernel, dim3(K), dim3(VF_FOLD_THREADS), 0, s, (const Fr*)v->d_fixed, (const uint8_t*)v->d_status,
+                     (const uint32_t*)v->d_circuit, lo, hi, (const G1Affine*)v->d_bases, K, v->d_partial);
+        PLONK_LAUNCH(verify_fold_multi_kernel, dim3(1), dim3(VF_FOLD_THREADS), 0, s, (const G1Xyzz*)v->d_lr, (const uint8_t*)v->d_status, lo, hi,
+                     (const G1Xyzz*)v->d_partial, K + 1, v->d_out, d_flags);
+    }
     PLONK_CHECK_HIP(hipGetLastError());
     PLONK_CHECK_HIP(hipMemcpyAsync(out_L, v->d_out, 64, hipMemcpyDeviceToHost, s));
     PLONK_CHECK_HIP(hipMemcpyAsync(out_R, v->d_out + 2, 64, hipMemcpyDeviceToHost, s));

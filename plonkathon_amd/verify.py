@@ -1,10 +1,13 @@
-"""`BatchVerifier` — N proofs of one circuit checked with one pairing product.
+"""`BatchVerifier` — N proofs of one circuit checked with one pairing product; `MultiBatchVerifier` — the same for a batch mixed
+of the circuits of a table (one setup).
 
 The reference verifies one proof per call (TESTING_verifier_DO_NOT_OPEN.py:39-163): e(L, [x]_2) == e(R, [1]_2) with L, R in G1.
 For a batch the device computes every proof's L_i and R_i (transcript replay, field arithmetic and eleven scalar
 multiplications per proof: plonk_verifier_* in include/plonk_hip.h), folds them under random 128-bit weights rho_i, and the host
 asks `pairing_check` once: e(sum rho_i L_i, [x]_2) == e(sum rho_i R_i, [1]_2).  Honest batches always pass; a batch holding a bad
-proof passes with probability about 2^-128.
+proof passes with probability about 2^-128.  The check is over the same [x]_2 whatever circuit a proof belongs to, so proofs of
+several circuits of one setup fold together: only the eight key points a proof's fixed scalars multiply are its circuit's
+(plonk_verifier_create_multi, _load_multi, _load_provers).
 """
 import ctypes
 import os
@@ -24,16 +27,26 @@ def _point_bytes(pt):
     return bytes(64) if pt is None else int(pt[0]).to_bytes(32, "little") + int(pt[1]).to_bytes(32, "little")
 
 
-class BatchVerifier:
-    def __init__(self, vk, n_public: int, ctx=None):
-        """`vk`: the VerificationKey of `Setup.verification_key(...)`; `n_public`: public inputs per proof."""
-        self.vk, self.n_public = vk, int(n_public)
+def _key_bytes(vk):
+    return b"".join(_point_bytes(p) for p in (vk.Qm, vk.Ql, vk.Qr, vk.Qo, vk.Qc, vk.S1, vk.S2, vk.S3))
+
+
+def _public_row(row, n_public):
+    row = [int(x) for x in row]
+    assert len(row) == n_public, "a row of %d public inputs, the circuit has %d" % (len(row), n_public)
+    assert all(0 <= x < (1 << 256) for x in row), "a public input is not a canonical Fr value"
+    return b"".join(x.to_bytes(32, "little") for x in row)
+
+
+class _Verifier:
+    """What the two verifiers share: a plonk_verifier handle, the forms proofs come in, folds, the pairing check and bisection."""
+
+    def __init__(self, vk, ctx):
+        self.vk = vk  # its X_2 is the one the pairing check is over
         self.ctx = ctx or get_context()
         self.status, self.pairing_checks = b"", 0
         self._batch = 0
-        blob = b"".join(_point_bytes(p) for p in (vk.Qm, vk.Ql, vk.Qr, vk.Qo, vk.Qc, vk.S1, vk.S2, vk.S3))
         self._h = ctypes.c_void_p()
-        check(self.ctx.L.plonk_verifier_create(self.ctx.handle, _log2_exact(vk.group_order), blob, self.n_public, ctypes.byref(self._h)))
 
     def __del__(self):
         try:
@@ -80,37 +93,11 @@ class BatchVerifier:
             out.append(b"".join(blob[480 * i + 288 + 32 * e : 480 * i + 320 + 32 * e][::-1] for e in range(6)))  # big-endian there
         return b"".join(out)
 
-    def _publics(self, publics):
-        rows = []
-        for row in publics:
-            row = [int(x) for x in row]
-            assert len(row) == self.n_public, "a row of %d public inputs, the circuit has %d" % (len(row), self.n_public)
-            assert all(0 <= x < (1 << 256) for x in row), "a public input is not a canonical Fr value"
-            rows.append(b"".join(x.to_bytes(32, "little") for x in row))
-        return b"".join(rows)
-
     @staticmethod
     def _seed(seed):
         seed = os.urandom(32) if seed is None else bytes(seed)
         assert len(seed) == 32, "seed: 32 bytes"
         return seed
-
-    def load(self, proofs, publics, seed=None):
-        """Per-proof work on the device: status bytes, weighted scalars, scalar multiplications, L_i and R_i."""
-        publics = list(publics)
-        B = len(publics)
-        pub = self._publics(publics)
-        rec = self._records(proofs, B)
-        self._batch = 0
-        check(self.ctx.L.plonk_verifier_load(self._h, rec, pub if self.n_public else None, B, self._seed(seed)))
-        self._loaded(B)
-
-    def load_prover(self, batch_prover, B=None, seed=None):
-        """The same for the batch resident in a BatchProver (after run()): the proofs never leave the device."""
-        B = batch_prover._resident if B is None else B
-        self._batch = 0
-        check(self.ctx.L.plonk_verifier_load_prover(self._h, batch_prover._h, B, self._seed(seed)))
-        self._loaded(B)
 
     def _loaded(self, B):
         st = ctypes.create_string_buffer(B)
@@ -160,6 +147,34 @@ class BatchVerifier:
         split(0, B)
         return res
 
+
+class BatchVerifier(_Verifier):
+    def __init__(self, vk, n_public: int, ctx=None):
+        """`vk`: the VerificationKey of `Setup.verification_key(...)`; `n_public`: public inputs per proof."""
+        super().__init__(vk, ctx)
+        self.n_public = int(n_public)
+        check(self.ctx.L.plonk_verifier_create(self.ctx.handle, _log2_exact(vk.group_order), _key_bytes(vk), self.n_public, ctypes.byref(self._h)))
+
+    def _publics(self, publics):
+        return b"".join(_public_row(row, self.n_public) for row in publics)
+
+    def load(self, proofs, publics, seed=None):
+        """Per-proof work on the device: status bytes, weighted scalars, scalar multiplications, L_i and R_i."""
+        publics = list(publics)
+        B = len(publics)
+        pub = self._publics(publics)
+        rec = self._records(proofs, B)
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load(self._h, rec, pub if self.n_public else None, B, self._seed(seed)))
+        self._loaded(B)
+
+    def load_prover(self, batch_prover, B=None, seed=None):
+        """The same for the batch resident in a BatchProver (after run()): the proofs never leave the device."""
+        B = batch_prover._resident if B is None else B
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load_prover(self._h, batch_prover._h, B, self._seed(seed)))
+        self._loaded(B)
+
     def verify(self, proofs, publics, seed=None) -> bool:
         """True iff every proof is well-formed and the fold over the whole batch passes the pairing check.  `proofs`: bytes of
         768-byte records, bytes of 480-byte compressed records (BatchProver.download_compressed) or a list of Proof objects;
@@ -182,4 +197,69 @@ class BatchVerifier:
 
     def verify_each_prover(self, batch_prover, B=None, seed=None):
         self.load_prover(batch_prover, B, seed)
+        return self._verdicts()
+
+
+class MultiBatchVerifier(_Verifier):
+    """A batch mixed of the circuits of a table, one pairing check.  The circuits must be of ONE setup: the argument folds checks
+    over the same [x]_2, so keys of different setups are refused, not verified separately."""
+
+    MAX_CIRCUITS = 64  # PLONK_VERIFIER_MAX_CIRCUITS
+
+    def __init__(self, circuits, ctx=None):
+        """`circuits`: a list of (vk, n_public); a proof's circuit id is its circuit's position in that list."""
+        circuits = [(vk, int(l)) for vk, l in circuits]
+        K = len(circuits)
+        assert 1 <= K <= self.MAX_CIRCUITS, "%d circuits: a table holds 1 to %d" % (K, self.MAX_CIRCUITS)
+        assert all(vk.X_2 == circuits[0][0].X_2 for vk, _ in circuits), "the verification keys are of different setups ([x]_2 differs)"
+        super().__init__(circuits[0][0], ctx)
+        self.vks, self.n_public = [vk for vk, _ in circuits], [l for _, l in circuits]
+        log_n = (ctypes.c_uint * K)(*[_log2_exact(vk.group_order) for vk in self.vks])
+        n_public = (ctypes.c_size_t * K)(*self.n_public)
+        check(self.ctx.L.plonk_verifier_create_multi(self.ctx.handle, K, log_n, b"".join(_key_bytes(vk) for vk in self.vks), n_public, ctypes.byref(self._h)))
+
+    def _ids(self, circuit_ids):
+        ids = [int(c) for c in circuit_ids]
+        assert all(0 <= c < len(self.vks) for c in ids), "a circuit id is outside the table of %d circuits" % len(self.vks)
+        return ids
+
+    def load(self, proofs, circuit_ids, publics, seed=None):
+        """As BatchVerifier.load; `circuit_ids[i]` is the circuit of proof i and `publics[i]` a row of that circuit's length."""
+        ids, publics = self._ids(circuit_ids), list(publics)
+        B = len(ids)
+        assert len(publics) == B, "%d circuit ids, %d rows of public inputs" % (B, len(publics))
+        pub = b"".join(_public_row(row, self.n_public[c]) for row, c in zip(publics, ids))
+        rec = self._records(proofs, B)
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load_multi(self._h, rec, (ctypes.c_uint32 * B)(*ids), pub or None, len(pub) // 32, B, self._seed(seed)))
+        self._loaded(B)
+
+    def load_provers(self, provers, seed=None):
+        """`provers`: [(circuit_id, BatchProver), ...], each after run().  The batch is their resident batches one after the other
+        in list order; the proofs never leave the device."""
+        provers = list(provers)
+        ids = self._ids(c for c, _ in provers)
+        n = len(provers)
+        B = sum(bp._resident for _, bp in provers)
+        self._batch = 0
+        handles = (ctypes.c_void_p * n)(*[bp._h.value for _, bp in provers])
+        check(self.ctx.L.plonk_verifier_load_provers(self._h, n, handles, (ctypes.c_uint32 * n)(*ids), self._seed(seed)))
+        self._loaded(B)
+
+    def verify(self, proofs, circuit_ids, publics, seed=None) -> bool:
+        """BatchVerifier.verify for a mixed batch: one pairing check for all of it."""
+        self.load(proofs, circuit_ids, publics, seed)
+        return self._verdict()
+
+    def verify_each(self, proofs, circuit_ids, publics, seed=None):
+        """One verdict per position, by bisection over positions: the sub-ranges cut across circuits."""
+        self.load(proofs, circuit_ids, publics, seed)
+        return self._verdicts()
+
+    def verify_provers(self, provers, seed=None) -> bool:
+        self.load_provers(provers, seed)
+        return self._verdict()
+
+    def verify_each_provers(self, provers, seed=None):
+        self.load_provers(provers, seed)
         return self._verdicts()

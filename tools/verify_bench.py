@@ -10,7 +10,15 @@ At group_order 2^11, for B = 512 and B = 10 240 proofs of the chain circuit on t
   (d) VerificationKey.verify_proof on 16 proofs of the same batch, per proof.
 Ratios: (a) / (c) — wanted <= 0.10 at B = 10 240 — and (d) x B / ((a) + (b)).
 
-usage: python tools/verify_bench.py [--batches 512,10240] [--bench-json FILE | --no-bench] [--out profiles/verify_batch.json]"""
+`--circuits K[,K...]` adds the mixed leg -> profiles/verify_multi.json: K distinct 2^11 circuits (the chain with another constant
+added in its last row per circuit), `--total` resident proofs split evenly over K provers, checked
+  (m) by one MultiBatchVerifier: device part of verify_provers — plonk_verifier_load_provers + plonk_verifier_fold(0, B) — median of
+      5; beside it one fold of a half range (what every bisection step costs) and the one host pairing check;
+  (s) by K BatchVerifiers of B / K proofs each: the sum of their device parts, and their K host pairing checks.
+`--batches ""` skips the one-circuit legs.
+
+usage: python tools/verify_bench.py [--batches 512,10240] [--bench-json FILE | --no-bench] [--out profiles/verify_batch.json]
+                                    [--circuits 4,16] [--total 10240] [--multi-out profiles/verify_multi.json]"""
 import argparse
 import ctypes
 import json
@@ -31,11 +39,15 @@ def main():
     ap.add_argument("--bench-json", default="", help="a file holding bench.py's result line (skips the child run)")
     ap.add_argument("--no-bench", action="store_true", help="leave (c) and the ratio (a) / (c) unmeasured")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "verify_batch.json"))
+    ap.add_argument("--circuits", default="", help="table sizes K of the mixed leg, e.g. 4,16")
+    ap.add_argument("--total", type=int, default=10240, help="resident proofs of the mixed leg, split evenly over the K circuits")
+    ap.add_argument("--multi-out", default=os.path.join(REPO, "profiles", "verify_multi.json"))
     args = ap.parse_args()
 
     import bench
     from bench_legs import ClockSampler
-    from plonkathon_amd import BatchProver, BatchVerifier, Program, Setup, get_context
+    from plonkathon_amd import BatchProver, BatchVerifier, MultiBatchVerifier, Program, Setup, get_context
+    from plonkathon_amd.field import R_MOD
     from plonkathon_amd._lib import check
 
     n = bench.GROUP_ORDER = 2048
@@ -52,7 +64,59 @@ def main():
         check(ctx.L.plonk_timer_stop_ms(ctx.handle, ctypes.byref(ms)))
         return ms.value, out
 
-    for B in [int(x) for x in args.batches.split(",")]:
+    def mixed_leg(K):
+        per = args.total // K
+        B = per * K
+        provers, vks = [], []
+        for c in range(K):
+            lines = bench.chain_program_lines(n)
+            if c:
+                lines[-1] += " + %d" % c
+            prog = Program(lines, n)
+            vks.append(setup.verification_key(prog.common_preprocessed_input()))
+            wits = []
+            for i in range(per):
+                w = bench.witness_for(c * per + i)
+                w["x%d" % (n - 1)] = (w["x%d" % (n - 1)] + c) % R_MOD
+                wits.append(w)
+            bp = BatchProver(setup, prog)
+            bp.upload(wits)
+            bp.run()
+            assert not any(bp.download_raw()[1])
+            provers.append(bp)
+        labelled = list(enumerate(provers))
+        mv = MultiBatchVerifier([(vk, 1) for vk in vks])
+        singles = [BatchVerifier(vk, 1) for vk in vks]
+        assert mv.verify_provers(labelled)  # warm-up: code objects, allocations
+        assert all(bv.verify_prover(bp) for bv, bp in zip(singles, provers))
+        sampler = ClockSampler(0)
+        sampler.start()
+        m_dev, m_half, m_pair, s_dev, s_pair = [], [], [], [], []
+        for _ in range(5):  # the two ways alternate
+            ms, (L, R) = timed(lambda: (mv.load_provers(labelled), mv.fold(0, B))[1])
+            m_dev.append(ms)
+            m_half.append(timed(lambda: mv.fold(0, B // 2))[0])
+            t0 = time.perf_counter()
+            assert mv.check_pairing(L, R)
+            m_pair.append(1e3 * (time.perf_counter() - t0))
+            ms, folds = timed(lambda: [(bv.load_prover(bp), bv.fold(0, per))[1] for bv, bp in zip(singles, provers)])
+            s_dev.append(ms)
+            t0 = time.perf_counter()
+            assert all(bv.check_pairing(L, R) for bv, (L, R) in zip(singles, folds))
+            s_pair.append(1e3 * (time.perf_counter() - t0))
+        med = statistics.median
+        return {"circuits": K, "batch": B, "m_device_ms_median_of_5": med(m_dev), "m_device_ms_all": m_dev, "m_half_range_fold_ms_median_of_5": med(m_half),
+                "m_host_pairing_ms_median_of_5": med(m_pair), "s_device_ms_sum_median_of_5": med(s_dev), "s_device_ms_sum_all": s_dev,
+                "s_host_pairings_ms_median_of_5": med(s_pair), "m_total_ms": med(m_dev) + med(m_pair), "s_total_ms": med(s_dev) + med(s_pair),
+                "clocks": sampler.summary()}
+
+    if args.circuits:
+        multi = {"group_order": n, "device": ctx.name(), "runs": [mixed_leg(int(k)) for k in args.circuits.split(",")]}
+        with open(args.multi_out, "w") as f:
+            json.dump(multi, f, indent=1)
+        print(json.dumps(multi))
+
+    for B in [int(x) for x in args.batches.split(",") if x]:
         wits = [bench.witness_for(i) for i in range(B)]
         bp = BatchProver(setup, program)
         bp.upload(wits)
@@ -82,6 +146,8 @@ def main():
                             "b_host_pairing_ms_median_of_5": b, "d_verify_proof_ms_per_proof": one_ms,
                             "speedup_d_x_B_over_a_plus_b": one_ms * B / (a + b), "clocks": clocks})
         del bv, bp
+    if not rec["runs"]:
+        return
     if args.bench_json:
         line = [l for l in open(args.bench_json).read().splitlines() if l.startswith("{")][-1]
     elif not args.no_bench:
