@@ -489,6 +489,25 @@ int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[6
 int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_scalars_le32, size_t count, uint8_t* h_out_xy_le,
                       uint8_t* h_out_is_identity);
 
+/* ---- per-proof verdicts in one pass: pairing checks on the device --------------------------------------
+ * A batch that fails its one pairing check holds bad proofs; naming them by bisection costs a fold and a host pairing per probe,
+ * in series, and grows with their number.  Every proof's own check e(L_i, [x]_2) == e(R_i, [1]_2) is over the same two G2 points,
+ * so the lines of the ate loop over them are computed once and `count` checks run one per lane in ONE launch, whatever their verdicts.
+ *   plonk_pairing_check_many   out_ok[i] = 1 iff e(A_i, Q0) e(B_i, Q1) == 1.  g2_le = Q0, Q1 and g1_xy_le = [count][2] points A_i, B_i
+ *                           in plonk_pairing_check's encodings, g1_is_identity = [count][2] flags (a flagged point contributes
+ *                           nothing).  PLONK_ERR_ARG: a coordinate not below p, a point off its curve, Q0 or Q1 the identity (a
+ *                           fixed table needs a point), count == 0.
+ *   plonk_verifier_set_x2      builds and uploads the line tables of [x]_2 (canonical x.c0||x.c1||y.c0||y.c1 LE; PLONK_ERR_ARG if it
+ *                           is not on the twist) and of the generator [1]_2.  Once per verifier; it changes nothing else.
+ *   plonk_verifier_check_each  out_ok[i], i < batch: 0 where status[i] != 0 (no pairing is done for that proof), else the verdict of
+ *                           the proof's OWN check — L_i as kept, R_i completed by its nine fixed-point products (the key points of
+ *                           the proof's circuit, and G1).  PLONK_ERR_STATE before plonk_verifier_set_x2 or with no batch loaded.
+ *                           Nothing plonk_verifier_fold reads is changed.                                                      */
+int plonk_pairing_check_many(plonk_ctx* ctx, const uint8_t g2_le[2][128], const uint8_t* g1_xy_le, const uint8_t* g1_is_identity, size_t count,
+                             uint8_t* out_ok);
+int plonk_verifier_set_x2(plonk_verifier* v, const uint8_t x2_le[128]);
+int plonk_verifier_check_each(plonk_verifier* v, uint8_t* out_ok);
+
 /* ---- Fiat-Shamir transcript (host) ----------------------------------------------------------------
  * Replaces `merlin.MerlinTranscript` (third-party) as subclassed by transcript.py:58-60:
  *   plonk_transcript_new              MerlinTranscript(label)             (prover.py:53 uses b"plonk")

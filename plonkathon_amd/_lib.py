@@ -125,6 +125,9 @@ SIGNATURES = {
     "plonk_verifier_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "plonk_verifier_fold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),
     "plonk_g1_mul_many": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p]),
+    "plonk_pairing_check_many": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_size_t, ctypes.c_char_p]),
+    "plonk_verifier_set_x2": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "plonk_verifier_check_each": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "plonk_transcript_new": (ctypes.c_int, [_u8p, ctypes.c_size_t, c_void_pp]),
     "plonk_transcript_clone": (ctypes.c_int, [ctypes.c_void_p, c_void_pp]),
     "plonk_transcript_free": (ctypes.c_int, [ctypes.c_void_p]),

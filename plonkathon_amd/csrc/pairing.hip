@@ -14,70 +14,15 @@
 //     yP - (L xP) w + (L xR - yR) w^3         (vertical lines vanish under the final exponentiation).
 // The final exponentiation is a plain square-and-multiply by the 2790-bit constant of pairing_constants.h.
 // Runs on the CPU by design ("Verifier + pairing on CPU"); it shares fp.h with the kernels
-// (the field templates are __host__ __device__) and nothing with oracle/.
+// (the field templates are __host__ __device__) and the tower of pairing_tower.h with the per-lane checks of pairing_device.h,
+// and nothing with oracle/.
 #include <string.h>
 
 #include "pairing_constants.h"
 #include "plonk_internal.h"
+#include "pairing_tower.h"
 
 namespace {
-
-struct Fq2 { Fq c0, c1; };
-struct Fq6 { Fq2 c0, c1, c2; };
-struct Fq12 { Fq6 c0, c1; };
-
-inline Fq fq_zero() { return fp_zero<FqParams>(); }
-inline Fq fq_one() { return fp_one<FqParams>(); }
-inline Fq fq_small(uint32_t k) {
-    Fq a = fq_zero();
-    a.v[0] = k;
-    return fp_to_mont(a);
-}
-
-inline Fq2 f2_zero() { return Fq2{fq_zero(), fq_zero()}; }
-inline Fq2 f2_one() { return Fq2{fq_one(), fq_zero()}; }
-inline bool f2_is_zero(const Fq2& a) { return fp_is_zero(a.c0) && fp_is_zero(a.c1); }
-inline bool f2_eq(const Fq2& a, const Fq2& b) { return fp_eq(a.c0, b.c0) && fp_eq(a.c1, b.c1); }
-inline Fq2 f2_add(const Fq2& a, const Fq2& b) { return Fq2{fp_add(a.c0, b.c0), fp_add(a.c1, b.c1)}; }
-inline Fq2 f2_sub(const Fq2& a, const Fq2& b) { return Fq2{fp_sub(a.c0, b.c0), fp_sub(a.c1, b.c1)}; }
-inline Fq2 f2_neg(const Fq2& a) { return Fq2{fp_neg(a.c0), fp_neg(a.c1)}; }
-inline Fq2 f2_mul(const Fq2& a, const Fq2& b) {  // (a0 + a1 i)(b0 + b1 i), i^2 = -1
-    const Fq t0 = fp_mul(a.c0, b.c0), t1 = fp_mul(a.c1, b.c1);
-    const Fq s = fp_mul(fp_add(a.c0, a.c1), fp_add(b.c0, b.c1));
-    return Fq2{fp_sub(t0, t1), fp_sub(fp_sub(s, t0), t1)};
-}
-inline Fq2 f2_mul_fq(const Fq2& a, const Fq& k) { return Fq2{fp_mul(a.c0, k), fp_mul(a.c1, k)}; }
-inline Fq2 f2_mul_xi(const Fq2& a) {  // (9 + i)(a0 + a1 i) = (9 a0 - a1) + (9 a1 + a0) i
-    const Fq nine = fq_small(9);
-    return Fq2{fp_sub(fp_mul(a.c0, nine), a.c1), fp_add(fp_mul(a.c1, nine), a.c0)};
-}
-inline Fq2 f2_inv(const Fq2& a) {  // conj(a) / (a0^2 + a1^2)
-    const Fq n = fp_inv(fp_add(fp_sqr(a.c0), fp_sqr(a.c1)));
-    return Fq2{fp_mul(a.c0, n), fp_neg(fp_mul(a.c1, n))};
-}
-
-inline Fq6 f6_zero() { return Fq6{f2_zero(), f2_zero(), f2_zero()}; }
-inline Fq6 f6_add(const Fq6& a, const Fq6& b) { return Fq6{f2_add(a.c0, b.c0), f2_add(a.c1, b.c1), f2_add(a.c2, b.c2)}; }
-inline Fq6 f6_sub(const Fq6& a, const Fq6& b) { return Fq6{f2_sub(a.c0, b.c0), f2_sub(a.c1, b.c1), f2_sub(a.c2, b.c2)}; }
-inline Fq6 f6_mul(const Fq6& a, const Fq6& b) {  // v^3 = xi
-    const Fq2 t0 = f2_mul(a.c0, b.c0), t1 = f2_mul(a.c1, b.c1), t2 = f2_mul(a.c2, b.c2);
-    const Fq2 m12 = f2_sub(f2_sub(f2_mul(f2_add(a.c1, a.c2), f2_add(b.c1, b.c2)), t1), t2);  // a1 b2 + a2 b1
-    const Fq2 m01 = f2_sub(f2_sub(f2_mul(f2_add(a.c0, a.c1), f2_add(b.c0, b.c1)), t0), t1);  // a0 b1 + a1 b0
-    const Fq2 m02 = f2_sub(f2_sub(f2_mul(f2_add(a.c0, a.c2), f2_add(b.c0, b.c2)), t0), t2);  // a0 b2 + a2 b0
-    return Fq6{f2_add(t0, f2_mul_xi(m12)), f2_add(m01, f2_mul_xi(t2)), f2_add(m02, t1)};
-}
-inline Fq6 f6_mul_v(const Fq6& a) { return Fq6{f2_mul_xi(a.c2), a.c0, a.c1}; }
-
-inline Fq12 f12_one() { return Fq12{Fq6{f2_one(), f2_zero(), f2_zero()}, f6_zero()}; }
-inline Fq12 f12_mul(const Fq12& a, const Fq12& b) {  // w^2 = v
-    const Fq6 t0 = f6_mul(a.c0, b.c0), t1 = f6_mul(a.c1, b.c1);
-    const Fq6 m = f6_sub(f6_sub(f6_mul(f6_add(a.c0, a.c1), f6_add(b.c0, b.c1)), t0), t1);
-    return Fq12{f6_add(t0, f6_mul_v(t1)), m};
-}
-inline bool f12_is_one(const Fq12& a) {
-    return fp_eq(a.c0.c0.c0, fq_one()) && fp_is_zero(a.c0.c0.c1) && f2_is_zero(a.c0.c1) && f2_is_zero(a.c0.c2) && f2_is_zero(a.c1.c0) &&
-           f2_is_zero(a.c1.c1) && f2_is_zero(a.c1.c2);
-}
 
 struct G2Aff { Fq2 x, y; bool inf; };
 

@@ -12,12 +12,16 @@
 //                           fixed-point products (their scalars are summed over the range in Fr first) -> two affine points
 // A table of K > 1 circuits folds with verify_fold_circuit_kernel (one workgroup per circuit: its eight key-point sums and
 // products -> one partial point) and verify_fold_multi_kernel (L, R over the range + the partials) in place of the last.
+// Per-proof verdicts without bisection (plonk_verifier_check_each): verify_fixed_products_kernel (the nine fixed-point products of
+// EVERY proof, which the folds only ever form over a range), verify_own_points_kernel (L_b and -R_b complete, affine) and the
+// per-lane pairing check of pairing_device.h over the line tables of [x]_2 and [1]_2 (plonk_verifier_set_x2).
 #include <string.h>
 
 #include "plonk_internal.h"
 #include "transcript.h"
 #include "transcript_device.h"
 #include "prover.h"
+#include "pairing_device.h"
 
 #define VF_OWN 11    // a_1, b_1, c_1, z_1, t_lo_1, t_mid_1, t_hi_1, W_z_1, W_zw_1 in R_i;  W_z_1, W_zw_1 in L_i
 #define VF_FIXED 9   // Qm, Ql, Qr, Qo, Qc, S1, S2, S3, G1
@@ -385,6 +389,43 @@ __global__ void __launch_bounds__(VF_FOLD_THREADS) verify_fold_multi_kernel(cons
     vf_fold_out(total, red, 1, out_xy, out_flags, tid);
 }
 
+// check_each, one lane per (proof, fixed term k): prod[9 b + k] = fixed[b][k] * (Qm .. S3 of the proof's circuit, k < 8; G1, k = 8);
+// the identity for a proof that is not well-formed.  circuit == nullptr: every proof is of circuit 0.
+__global__ void __launch_bounds__(64) verify_fixed_products_kernel(const Fr* fixed, const uint8_t* status, const uint32_t* circuit, const G1Affine* bases,
+                                                                   unsigned K, size_t B, G1Xyzz* prod) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * VF_FIXED) return;
+    const size_t b = j / VF_FIXED;
+    const unsigned k = (unsigned)(j % VF_FIXED);
+    if (status[b]) {
+        vf_store_xyzz(prod + j, g1_xyzz_identity());
+        return;
+    }
+    const G1Affine* base = k < VF_FIXED - 1 ? bases + (size_t)(circuit ? circuit[b] : 0) * (VF_FIXED - 1) + k : bases + (size_t)K * (VF_FIXED - 1);
+    G1Affine p;
+    p.x = fp_load(&base->x);
+    p.y = fp_load(&base->y);
+    vf_store_xyzz(prod + j, g1_mul_affine(p, fp_from_mont(fp_load(fixed + j))));
+}
+// check_each, one lane per (proof, side): pts[2 b] = L_b, pts[2 b + 1] = -(R_b + the proof's nine fixed-point products), affine with
+// (0, 0) for the identity: the proof's own check is e(pts[2 b], [x]_2) e(pts[2 b + 1], [1]_2) == 1.  Reads lr, writes none of it.
+__global__ void __launch_bounds__(64) verify_own_points_kernel(const G1Xyzz* lr, const G1Xyzz* prod, const uint8_t* status, size_t B, G1Affine* pts) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 2 * B) return;
+    const size_t b = j >> 1;
+    G1Affine r = g1_affine_identity();
+    if (!status[b]) {
+        G1Xyzz acc = vf_load_xyzz(lr + j);
+        if (j & 1)
+#pragma unroll 1
+            for (unsigned k = 0; k < VF_FIXED; k++) g1_add(acc, vf_load_xyzz(prod + b * VF_FIXED + k));
+        r = g1_to_affine(acc);
+        if (j & 1) r = g1_affine_neg(r);
+    }
+    fp_store(&pts[j].x, r.x);
+    fp_store(&pts[j].y, r.y);
+}
+
 // plonk_g1_mul_many's marshalling: canonical points -> Montgomery form with the range / curve tests, products -> canonical affine
 __global__ void g1_mul_many_in_kernel(Fq* xy, const Fr* scalars, size_t count, uint32_t* bad) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -444,6 +485,7 @@ struct plonk_verifier {
     Fq* d_out;               // [4] + 2 flag bytes behind them
     hipEvent_t* evs;         // [n_evs] a prover's pack is done (plonk_verifier_load_prover, _load_provers: one per prover)
     size_t n_evs;
+    PairingLine* d_lines;    // [2][PAIRING_ATE_LINES] the ate loop's lines over [x]_2 and over [1]_2 (plonk_verifier_set_x2; null before)
 };
 
 static void verifier_free_batch(plonk_verifier* v) {
@@ -630,7 +672,7 @@ int plonk_verifier_destroy(plonk_verifier* v) {
         hipStreamSynchronize(v->ctx->stream);
     }
     verifier_free_batch(v);
-    dev_free_all({(void**)&v->d_init, (void**)&v->d_bases, (void**)&v->d_circ, (void**)&v->d_partial, (void**)&v->d_out});
+    dev_free_all({(void**)&v->d_init, (void**)&v->d_bases, (void**)&v->d_circ, (void**)&v->d_partial, (void**)&v->d_out, (void**)&v->d_lines});
     for (size_t i = 0; i < v->n_evs; i++) hipEventDestroy(v->evs[i]);
     free(v->evs);
     free(v->h_circ);
@@ -766,6 +808,49 @@ int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[6
     PLONK_CHECK_HIP(hipMemcpyAsync(out_L, v->d_out, 64, hipMemcpyDeviceToHost, s));
     PLONK_CHECK_HIP(hipMemcpyAsync(out_R, v->d_out + 2, 64, hipMemcpyDeviceToHost, s));
     PLONK_CHECK_HIP(hipMemcpyAsync(out_is_identity, d_flags, 2, hipMemcpyDeviceToHost, s));
+    PLONK_CHECK_HIP(hipStreamSynchronize(s));
+    return PLONK_OK;
+}
+
+int plonk_verifier_set_x2(plonk_verifier* v, const uint8_t x2_le[128]) {
+    PLONK_REQUIRE(v && x2_le, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(v->ctx);
+    Fq2 x, y;
+    PLONK_TRY(pairing_g2_decode(x2_le, &x, &y));
+    std::vector<PairingLine> lines(2 * PAIRING_ATE_LINES);
+    pairing_line_table(x, y, lines.data());
+    pairing_line_table(pairing_g2_generator_x(), pairing_g2_generator_y(), lines.data() + PAIRING_ATE_LINES);
+    const size_t bytes = lines.size() * sizeof(PairingLine);
+    PLONK_CHECK_HIP(hipStreamSynchronize(v->ctx->stream));  // a check over the old tables may be running
+    if (!v->d_lines) PLONK_TRY(dev_alloc((void**)&v->d_lines, bytes));
+    PLONK_CHECK_HIP(hipMemcpy(v->d_lines, lines.data(), bytes, hipMemcpyHostToDevice));
+    return PLONK_OK;
+}
+
+int plonk_verifier_check_each(plonk_verifier* v, uint8_t* out_ok) {
+    PLONK_REQUIRE(v && out_ok, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(v->d_lines, PLONK_ERR_STATE, "check_each: plonk_verifier_set_x2 has not been called");
+    PLONK_REQUIRE(v->batch, PLONK_ERR_STATE, "no batch is loaded");
+    PLONK_ENTER(v->ctx);
+    const size_t B = v->batch, n_prod = B * VF_FIXED;
+    void* buf;
+    PLONK_TRY(ctx_scratch(v->ctx, 3, n_prod * sizeof(G1Xyzz) + 2 * B * sizeof(G1Affine) + B, &buf));
+    G1Xyzz* d_prod = (G1Xyzz*)buf;
+    G1Affine* d_pts = (G1Affine*)(d_prod + n_prod);
+    uint8_t* d_ok = (uint8_t*)(d_pts + 2 * B);
+    hipStream_t s = v->ctx->stream;
+    // (per-kernel times for tools/verify_bench.py --each: no-ops unless the context is profiling)
+    PLONK_TRY(prof_begin(v->ctx, "verify_each_fixed_products", (double)n_prod * sizeof(G1Xyzz)));
+    PLONK_LAUNCH(verify_fixed_products_kernel, dim3((unsigned)((n_prod + 63) / 64)), dim3(64), 0, s, (const Fr*)v->d_fixed, (const uint8_t*)v->d_status,
+                 v->n_circuits > 1 ? (const uint32_t*)v->d_circuit : (const uint32_t*)nullptr, (const G1Affine*)v->d_bases, v->n_circuits, B, d_prod);
+    PLONK_LAUNCH(verify_own_points_kernel, dim3((unsigned)((2 * B + 63) / 64)), dim3(64), 0, s, (const G1Xyzz*)v->d_lr, (const G1Xyzz*)d_prod,
+                 (const uint8_t*)v->d_status, B, d_pts);
+    PLONK_CHECK_HIP(hipGetLastError());
+    PLONK_TRY(prof_end(v->ctx));
+    PLONK_TRY(prof_begin(v->ctx, "verify_each_pairings", (double)B * 2 * sizeof(G1Affine)));
+    PLONK_TRY(pairing_check_fixed_launch(s, d_pts, v->d_lines, v->d_status, B, d_ok));
+    PLONK_TRY(prof_end(v->ctx));
+    PLONK_CHECK_HIP(hipMemcpyAsync(out_ok, d_ok, B, hipMemcpyDeviceToHost, s));
     PLONK_CHECK_HIP(hipStreamSynchronize(s));
     return PLONK_OK;
 }

@@ -61,6 +61,21 @@ def pairing_check(pairs) -> bool:
     return bool(ok.value)
 
 
+def pairing_check_many(pairs_q, points):
+    """[e(A_i, Q0) e(B_i, Q1) == 1 for (A_i, B_i) in `points`] with `pairs_q` = (Q0, Q1), two G2 points other than the identity:
+    one check per lane on the device, one launch (plonk_pairing_check_many).  A G1 point may be None, the identity."""
+    points = [(a, b) for a, b in points]
+    flat = [p for ab in points for p in ab]
+    g1 = b"".join(bytes(64) if p is None else le32(int(p[0])) + le32(int(p[1])) for p in flat)
+    flags = bytes(1 if p is None else 0 for p in flat)
+    g2 = b"".join(le32(int(q[0].coeffs[0])) + le32(int(q[0].coeffs[1])) + le32(int(q[1].coeffs[0])) + le32(int(q[1].coeffs[1])) for q in pairs_q)
+    assert len(g2) == 256, "pairs_q: two G2 points"
+    ctx = get_context()
+    ok = ctypes.create_string_buffer(max(len(points), 1))
+    check(ctx.L.plonk_pairing_check_many(ctx.handle, g2, g1, flags, len(points), ok))
+    return [b != 0 for b in ok.raw[: len(points)]]
+
+
 def _decode_points(xy: bytes, flags: bytes):
     out = []
     for i, f in enumerate(flags):

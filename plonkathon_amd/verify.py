@@ -8,6 +8,11 @@ asks `pairing_check` once: e(sum rho_i L_i, [x]_2) == e(sum rho_i R_i, [1]_2).  
 proof passes with probability about 2^-128.  The check is over the same [x]_2 whatever circuit a proof belongs to, so proofs of
 several circuits of one setup fold together: only the eight key points a proof's fixed scalars multiply are its circuit's
 (plonk_verifier_create_multi, _load_multi, _load_provers).
+
+Naming the bad proofs of a batch that failed (`verify_each`) is by bisection over folds by default: a fold launch and a host pairing
+per probe, so the cost grows with the number of bad proofs.  `device=True` replaces the bisection by ONE launch that runs every
+proof's own pairing check on the device, one lane per proof (plonk_verifier_check_each, csrc/pairing_device.h): the same cost
+whatever the number of bad proofs.
 """
 import ctypes
 import os
@@ -44,8 +49,9 @@ class _Verifier:
     def __init__(self, vk, ctx):
         self.vk = vk  # its X_2 is the one the pairing check is over
         self.ctx = ctx or get_context()
-        self.status, self.pairing_checks = b"", 0
+        self.status, self.pairing_checks, self.device_checks = b"", 0, 0
         self._batch = 0
+        self._x2_set = False  # the line tables of vk.X_2 and G2 are built at the first device check
         self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -102,7 +108,7 @@ class _Verifier:
     def _loaded(self, B):
         st = ctypes.create_string_buffer(B)
         check(self.ctx.L.plonk_verifier_status(self._h, st))
-        self.status, self._batch, self.pairing_checks = st.raw[:B], B, 0
+        self.status, self._batch, self.pairing_checks, self.device_checks = st.raw[:B], B, 0, 0
 
     # ---- folds and verdicts ---------------------------------------------------------------------
     def fold(self, lo, hi):
@@ -126,11 +132,25 @@ class _Verifier:
     def _verdict(self):
         return all(s == 0 for s in self.status) and self._check(0, self._batch)
 
-    def _verdicts(self):
+    def check_each_device(self):
+        """Every proof of the loaded batch under its OWN pairing check, on the device in one launch: [bool] per proof (False
+        without a pairing where the status byte is set).  `device_checks` counts the lanes."""
+        if not self._x2_set:
+            x, y = self.vk.X_2
+            check(self.ctx.L.plonk_verifier_set_x2(self._h, b"".join(int(c).to_bytes(32, "little") for c in x.coeffs + y.coeffs)))
+            self._x2_set = True
+        ok = ctypes.create_string_buffer(self._batch)
+        check(self.ctx.L.plonk_verifier_check_each(self._h, ok))
+        self.device_checks += self._batch
+        return [b != 0 for b in ok.raw[: self._batch]]
+
+    def _verdicts(self, device=False):
         B = self._batch
         res = [s == 0 for s in self.status]
         if self._check(0, B):
             return res
+        if device:
+            return self.check_each_device()
 
         def split(lo, hi):  # the fold over [lo, hi) is known to fail
             if hi - lo == 1:
@@ -184,20 +204,22 @@ class BatchVerifier(_Verifier):
         self.load(proofs, publics, seed)
         return self._verdict()
 
-    def verify_each(self, proofs, publics, seed=None):
+    def verify_each(self, proofs, publics, seed=None, device=False):
         """One verdict per proof.  The whole batch first; only if that fails, bisection by folds over sub-ranges (same weights,
-        nothing recomputed on the device but range sums): at most 2 k ceil(log2 B) + 1 pairing checks for k bad proofs."""
+        nothing recomputed on the device but range sums): at most 2 k ceil(log2 B) + 1 pairing checks for k bad proofs.
+        `device=True`: in place of the bisection, every proof's own pairing check on the device in one launch (`pairing_checks`
+        stays 1, `device_checks` = the batch size)."""
         self.load(proofs, publics, seed)
-        return self._verdicts()
+        return self._verdicts(device)
 
     def verify_prover(self, batch_prover, B=None, seed=None) -> bool:
         """verify() for the batch resident in `batch_prover` (after run()), without a trip through the host."""
         self.load_prover(batch_prover, B, seed)
         return self._verdict()
 
-    def verify_each_prover(self, batch_prover, B=None, seed=None):
+    def verify_each_prover(self, batch_prover, B=None, seed=None, device=False):
         self.load_prover(batch_prover, B, seed)
-        return self._verdicts()
+        return self._verdicts(device)
 
 
 class MultiBatchVerifier(_Verifier):
@@ -251,15 +273,16 @@ class MultiBatchVerifier(_Verifier):
         self.load(proofs, circuit_ids, publics, seed)
         return self._verdict()
 
-    def verify_each(self, proofs, circuit_ids, publics, seed=None):
-        """One verdict per position, by bisection over positions: the sub-ranges cut across circuits."""
+    def verify_each(self, proofs, circuit_ids, publics, seed=None, device=False):
+        """One verdict per position, by bisection over positions: the sub-ranges cut across circuits.  `device=True`: as
+        BatchVerifier.verify_each, each proof against the key points of its own circuit."""
         self.load(proofs, circuit_ids, publics, seed)
-        return self._verdicts()
+        return self._verdicts(device)
 
     def verify_provers(self, provers, seed=None) -> bool:
         self.load_provers(provers, seed)
         return self._verdict()
 
-    def verify_each_provers(self, provers, seed=None):
+    def verify_each_provers(self, provers, seed=None, device=False):
         self.load_provers(provers, seed)
-        return self._verdicts()
+        return self._verdicts(device)

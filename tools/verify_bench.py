@@ -17,8 +17,18 @@ added in its last row per circuit), `--total` resident proofs split evenly over 
   (s) by K BatchVerifiers of B / K proofs each: the sum of their device parts, and their K host pairing checks.
 `--batches ""` skips the one-circuit legs.
 
+`--each` runs the localisation leg instead -> profiles/verify_each.json: one batch resident in a BatchVerifier, B = 512 and 10 240, with
+k = 1, 16 and 256 proofs corrupted (a_eval + 1, spread evenly over the batch).  Medians of 5, device and host time together
+(time.perf_counter around the call), of
+  (l) load: the per-proof work every route starts from;
+  (b) verify_each's verdicts by bisection: folds and host pairings in series (`pairing_checks` beside it);
+  (d) the same verdicts by `device=True`: the whole-batch fold and its host pairing, then ONE plonk_verifier_check_each;
+and from plonk_profile_read the device time of check_each's two parts: the nine fixed-point products per proof with the two
+affine points, and the pairing kernel itself.
+
 usage: python tools/verify_bench.py [--batches 512,10240] [--bench-json FILE | --no-bench] [--out profiles/verify_batch.json]
-                                    [--circuits 4,16] [--total 10240] [--multi-out profiles/verify_multi.json]"""
+                                    [--circuits 4,16] [--total 10240] [--multi-out profiles/verify_multi.json]
+       python tools/verify_bench.py --each [--batches 512,10240] [--bad 1,16,256] [--each-out profiles/verify_each.json]"""
 import argparse
 import ctypes
 import json
@@ -42,6 +52,9 @@ def main():
     ap.add_argument("--circuits", default="", help="table sizes K of the mixed leg, e.g. 4,16")
     ap.add_argument("--total", type=int, default=10240, help="resident proofs of the mixed leg, split evenly over the K circuits")
     ap.add_argument("--multi-out", default=os.path.join(REPO, "profiles", "verify_multi.json"))
+    ap.add_argument("--each", action="store_true", help="the localisation leg: bisection against device=True")
+    ap.add_argument("--bad", default="1,16,256", help="numbers k of corrupted proofs of the localisation leg")
+    ap.add_argument("--each-out", default=os.path.join(REPO, "profiles", "verify_each.json"))
     args = ap.parse_args()
 
     import bench
@@ -109,6 +122,68 @@ def main():
                 "m_host_pairing_ms_median_of_5": med(m_pair), "s_device_ms_sum_median_of_5": med(s_dev), "s_device_ms_sum_all": s_dev,
                 "s_host_pairings_ms_median_of_5": med(s_pair), "m_total_ms": med(m_dev) + med(m_pair), "s_total_ms": med(s_dev) + med(s_pair),
                 "clocks": sampler.summary()}
+
+    def each_leg(B):
+        wits = [bench.witness_for(i) for i in range(B)]
+        bp = BatchProver(setup, program)
+        bp.upload(wits)
+        bp.run()
+        blob, status = bp.download_raw()
+        assert not any(status)
+        del bp
+        pubs = [[w["x0"]] for w in wits]
+        bv = BatchVerifier(vk, 1)
+        seed = bytes(range(32))
+        med = statistics.median
+
+        def wall(fn):
+            t0 = time.perf_counter()
+            out = fn()
+            return 1e3 * (time.perf_counter() - t0), out
+
+        rows = []
+        for k in [int(x) for x in args.bad.split(",") if x]:
+            bad = sorted({(2 * j + 1) * B // (2 * k) for j in range(k)})
+            recs = bytearray(blob)
+            for i in bad:  # a_eval + 1
+                e = int.from_bytes(recs[768 * i + 576 : 768 * i + 608], "little")
+                recs[768 * i + 576 : 768 * i + 608] = ((e + 1) % R_MOD).to_bytes(32, "little")
+            recs = bytes(recs)
+            want = [i not in set(bad) for i in range(B)]
+            assert bv.verify_each(recs, pubs, seed=seed, device=True) == want  # warm-up: code objects, allocations, the line tables
+            sampler = ClockSampler(0)
+            sampler.start()
+            load_ms, bis_ms, dev_ms, fixed_ms, pair_ms, checks = [], [], [], [], [], 0
+            for _ in range(5):  # the two routes alternate
+                load_ms.append(wall(lambda: bv.load(recs, pubs, seed))[0])
+                ms, got = wall(bv._verdicts)
+                assert got == want
+                bis_ms.append(ms)
+                checks = bv.pairing_checks
+                bv.load(recs, pubs, seed)
+                ctx.profile_reset()
+                ctx.profile(True)
+                ms, got = wall(lambda: bv._verdicts(device=True))
+                ctx.profile(False)
+                assert got == want and bv.pairing_checks == 1 and bv.device_checks == B
+                dev_ms.append(ms)
+                fixed_ms.append(ctx.profile_read("verify_each_fixed_products")[0])
+                pair_ms.append(ctx.profile_read("verify_each_pairings")[0])
+            rows.append({"batch": B, "bad": len(bad), "load_ms_median_of_5": med(load_ms), "bisection_ms_median_of_5": med(bis_ms), "bisection_ms_all": bis_ms,
+                         "bisection_pairing_checks": checks, "device_route_ms_median_of_5": med(dev_ms), "device_route_ms_all": dev_ms,
+                         "check_each_fixed_products_ms_median_of_5": med(fixed_ms), "check_each_pairing_kernel_ms_median_of_5": med(pair_ms),
+                         "check_each_pairing_kernel_ms_all": pair_ms, "device_route_over_bisection": med(dev_ms) / med(bis_ms), "clocks": sampler.summary()})
+            print(json.dumps(rows[-1]), flush=True)
+        return rows
+
+    if args.each:
+        each = {"group_order": n, "device": ctx.name(), "corruption": "a_eval + 1, spread evenly", "runs": []}
+        for B in [int(x) for x in args.batches.split(",") if x]:
+            each["runs"] += each_leg(B)
+        with open(args.each_out, "w") as f:
+            json.dump(each, f, indent=1)
+        print(json.dumps(each))
+        return
 
     if args.circuits:
         multi = {"group_order": n, "device": ctx.name(), "runs": [mixed_leg(int(k)) for k in args.circuits.split(",")]}
