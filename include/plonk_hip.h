@@ -253,6 +253,30 @@ typedef struct plonk_prover plonk_prover;
 int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
                         size_t n_public, plonk_prover** out);
 int plonk_prover_destroy(plonk_prover* p);
+/* ---- a prover over a table of circuits: proofs of several circuits of ONE setup and ONE group order in one lock-step batch.
+ * Circuits that need fewer rows are compiled (padded) at the common group order.  The proofs are byte for byte those of a
+ * plonk_prover_create prover of the proof's circuit; a table of one circuit is such a prover.  The same handle type: options,
+ * blinders, run, download, download_compressed, challenges and download_variables are the calls above and below.
+ *   plonk_prover_create_multi   n_circuits in 1 .. PLONK_PROVER_MAX_CIRCUITS (PLONK_ERR_ARG otherwise); selectors_le32[c][8][n] and
+ *                           n_public[c] as plonk_prover_create takes them, with the same tests.  Public rows are [l_max] wide, l_max the
+ *                           largest n_public[c], and zero beyond the proof's own circuit's count.
+ *   plonk_prover_set_wiring_multi   cell_index[c][3][n], public_index[c][l_max]: plonk_prover_set_wiring's tables per circuit.  One
+ *                           n_vars serves the table (a proof's variable row is [n_vars]); every circuit's variables are numbered in
+ *                           its own order; n_vars marks an empty cell and pads a circuit's public_index row (anything else there:
+ *                           PLONK_ERR_ARG).  plonk_prover_set_wiring on a table of more than one circuit: PLONK_ERR_STATE.
+ *   plonk_prover_set_labels circuit[b] < n_circuits (PLONK_ERR_ARG otherwise): the circuit of each proof of the NEXT upload, which must
+ *                           be of `batch` proofs (PLONK_ERR_STATE otherwise) — as plonk_prover_set_blinders serves the next run.  With
+ *                           more than one circuit an upload without labels pending is PLONK_ERR_STATE; with one they are optional.
+ *                           The labels stay with the batch the upload makes resident.  plonk_prover_upload_witness refuses a non-zero
+ *                           public value beyond the proof's circuit's count (PLONK_ERR_ARG).
+ * NOT on a table of more than one circuit (PLONK_ERR_STATE, the prover stays usable): the witness solver (plonk_prover_set_inputs,
+ * plonk_prover_upload_inputs*, plonk_prover_solve_plan) and the two-slot intake (plonk_prover_stage_*, plonk_prover_advance) — the plan
+ * and the staged slot are per circuit.  Circuits of different group orders do not share a table.                                   */
+#define PLONK_PROVER_MAX_CIRCUITS 64
+int plonk_prover_create_multi(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, size_t n_circuits, const uint8_t* selectors_le32,
+                              const size_t* n_public, plonk_prover** out);
+int plonk_prover_set_wiring_multi(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars);
+int plonk_prover_set_labels(plonk_prover* p, const uint32_t* circuit, size_t batch);
 /* options (0 = default): PLONK_PROVER_LAGRANGE_COMMITS commits a_1, b_1, c_1 and z_1 (rounds 1-2) from their
  * Lagrange values over plonk_srs_lagrange instead of from coefficient forms — same group elements, same proof. */
 #define PLONK_PROVER_LAGRANGE_COMMITS 1u
@@ -484,6 +508,11 @@ int plonk_verifier_create_multi(plonk_ctx* ctx, size_t n_circuits, const unsigne
 int plonk_verifier_load_multi(plonk_verifier* v, const uint8_t* proofs768, const uint32_t* circuit, const uint8_t* public_le32,
                               size_t n_public_values, size_t batch, const uint8_t seed[32]);
 int plonk_verifier_load_provers(plonk_verifier* v, size_t n_provers, plonk_prover* const* provers, const uint32_t* circuit, const uint8_t seed[32]);
+/* the resident batch of a plonk_prover_create_multi prover, mixed as it is: proof b is of the verifier's circuit
+ * circuit_map[the prover's label of b] (circuit_map: one entry per circuit of the PROVER's table).  Errors as plonk_verifier_load_provers:
+ * PLONK_ERR_ARG for a mapped circuit whose (log_n, n_public) differs or for another device, PLONK_ERR_STATE without a resident batch.
+ * plonk_verifier_load_prover and plonk_verifier_load_provers refuse such a prover of more than one circuit (PLONK_ERR_ARG).        */
+int plonk_verifier_load_multi_prover(plonk_verifier* v, plonk_prover* p, const uint32_t* circuit_map, const uint8_t seed[32]);
 int plonk_verifier_status(plonk_verifier* v, uint8_t* out_status);
 int plonk_verifier_fold(plonk_verifier* v, size_t lo, size_t hi, uint8_t out_L[64], uint8_t out_R[64], uint8_t out_is_identity[2]);
 int plonk_g1_mul_many(plonk_ctx* ctx, const uint8_t* h_xy_le, const uint8_t* h_scalars_le32, size_t count, uint8_t* h_out_xy_le,

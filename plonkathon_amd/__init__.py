@@ -11,12 +11,12 @@ from .kzg import G1, G2, Z1, Setup, VerificationKey, ec_lincomb, ec_mul, g1_comp
 from .circuit import AssemblyEqn, Cell, Column, CommonPreprocessedInput, GateWires, Program  # noqa: F401
 from .fiat_shamir import Message1, Message2, Message3, Message4, Message5, Transcript  # noqa: F401
 from .plonk import Proof, Prover  # noqa: F401
-from .batch import BatchProver, ProofError  # noqa: F401
+from .batch import BatchProver, MultiBatchProver, ProofError  # noqa: F401
 from .verify import BatchVerifier, MultiBatchVerifier  # noqa: F401
 from .backend import Context, get_context, set_context  # noqa: F401
 
 __all__ = [
     "Scalar", "Fq", "Basis", "Polynomial", "Setup", "VerificationKey", "ec_lincomb", "ec_mul", "lincomb", "multisubset", "g1_compress", "g1_decompress", "pairing_check", "G1", "G2", "Z1",
     "Program", "CommonPreprocessedInput", "AssemblyEqn", "GateWires", "Column", "Cell", "Transcript", "Message1", "Message2",
-    "Message3", "Message4", "Message5", "Prover", "BatchProver", "BatchVerifier", "MultiBatchVerifier", "ProofError", "Proof", "Context", "get_context", "set_context",
+    "Message3", "Message4", "Message5", "Prover", "BatchProver", "MultiBatchProver", "BatchVerifier", "MultiBatchVerifier", "ProofError", "Proof", "Context", "get_context", "set_context",
 ]

@@ -77,6 +77,9 @@ SIGNATURES = {
     "plonk_g1_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "plonk_msm_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint]),
     "plonk_prover_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, _u8p, ctypes.c_size_t, c_void_pp]),
+    "plonk_prover_create_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_size_t, _u8p, ctypes.POINTER(ctypes.c_size_t), c_void_pp]),
+    "plonk_prover_set_wiring_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    "plonk_prover_set_labels": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]),
     "plonk_prover_set_options": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint]),
     "plonk_prover_set_blinders": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]),
     "plonk_prover_seed_blinders": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -121,6 +124,7 @@ SIGNATURES = {
     "plonk_verifier_load_prover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, _u8p]),
     "plonk_verifier_create_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint), _u8p, ctypes.POINTER(ctypes.c_size_t), c_void_pp]),
     "plonk_verifier_load_multi": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.POINTER(ctypes.c_uint32), _u8p, ctypes.c_size_t, ctypes.c_size_t, _u8p]),
+    "plonk_verifier_load_multi_prover": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), _u8p]),
     "plonk_verifier_load_provers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_void_pp, ctypes.POINTER(ctypes.c_uint32), _u8p]),
     "plonk_verifier_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "plonk_verifier_fold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]),

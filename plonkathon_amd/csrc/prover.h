@@ -77,16 +77,21 @@ struct plonk_prover {
         plonk_ctx* ctx;
         plonk_srs* srs;
         unsigned log_n;
-        size_t n, n_public;
+        size_t n, n_public;  // n_public: of the widest circuit of the table (l_max); public rows are [n_public], zero beyond a circuit's own count
+        // A prover over a table of K circuits of one group order (plonk_prover_create_multi): the three forms of the fixed polynomials,
+        // the wiring's two index tables hold the circuits one after the other, and every kernel that reads them takes the proof's
+        // circuit from Labels::dev.  K = 1 is plonk_prover_create's prover: its kernels get a null label array.
+        unsigned n_circuits;   // K
+        size_t* n_public_of;   // [K] host: each circuit's own number of public inputs
         Fr g;                // fixed coset offset (Montgomery)
         Fr w, n_inv, half;   // the n-th root of unity, 1 / n, 1 / 2
         // The quotient has degree < 3n, so THREE cosets of the n-th roots of unity determine it: x = g mu^r w^j, r < 3 (mu = the
         // 4n-th root of unity of prover.py:160), "coset-major" [r][j].  Every coset form below is [3][n] in that order.  A blinded
         // prover (prover_blind.h) takes all four: qcosets = 4, and plonk_prover_set_options rebuilds the coset forms as [4][n].
         unsigned qcosets;    // QCOSETS or QCOSETS_BLINDED
-        Fr* fixed_lag;       // [8][n]   Lagrange values
-        Fr* fixed_coef;      // [8][n]   coefficient forms
-        Fr* fixed_big;       // [8][3][n]  the circuit polynomials on the three cosets
+        Fr* fixed_lag;       // [K][8][n]   Lagrange values
+        Fr* fixed_coef;      // [K][8][n]   coefficient forms
+        Fr* fixed_big;       // [K][8][3][n]  the circuit polynomials on the three cosets
         Fr* l0_big;          // [3][n]
         Fr* x_big;           // [3][n]   the points g mu^r w^j
         Fr* g_pow;           // [3][n]   (g mu^r)^i: the load-side scaling of the size-n transform that evaluates on coset r
@@ -124,9 +129,9 @@ struct plonk_prover {
     } rounds;
     // ---- wiring (plonk_prover_set_wiring): the wire cells are scattered from per-variable values on the device
     struct Wiring {
-        uint32_t* cell_index;      // [3][n]  variable index of each wire cell; n_vars = empty cell / padding row
-        uint32_t* pub_index;       // [n_public]
-        uint32_t* cell_host;       // [3][n] host copy of cell_index (what plonk_prover_set_inputs plans from)
+        uint32_t* cell_index;      // [K][3][n]  variable index of each wire cell; n_vars = empty cell / padding row
+        uint32_t* pub_index;       // [K][n_public]  n_vars = a padding entry of a circuit with fewer public inputs: the value 0
+        uint32_t* cell_host;       // [K][3][n] host copy of cell_index (what plonk_prover_set_inputs plans from: K = 1 only)
         size_t n_vars;
     } wiring;
     // ---- intake and staging (prover_intake.h): the batch that is resident, and how its bytes came in
@@ -141,6 +146,16 @@ struct plonk_prover {
         unsigned long long* bad_input;  // device: index of the first uploaded value that was not below r, or ~0 (PROVER_ST_BAD_INPUT)
         size_t bad_stride;         // values per proof of the last upload that ran the checked conversion: *bad_input / bad_stride owns the bad value
     } intake;
+    // ---- the circuit of every proof (plonk_prover_set_labels): part of the resident batch, taken by the upload that follows the call
+    struct Labels {
+        uint32_t* pending;         // [pending_batch] host: the labels of the NEXT upload
+        size_t pending_batch;      // 0: none pending
+        uint32_t* host;            // [resident_b] host: the resident batch's (zeros where a K = 1 prover was given none); the verifier's load reads it
+        uint32_t* dev;             // [cap] device: what the kernels index the circuit table with (K > 1 only)
+        size_t cap, host_cap;
+        hipEvent_t copied;         // behind the copy host -> dev on the compute stream: `host` is not rewritten before it
+        bool copy_pending;
+    } labels;
     StagedSlot staged;             // the batch behind the resident one (plonk_prover_stage_*, plonk_prover_advance)
     // ---- the witness solver (witness_solve.h; plonk_prover_set_inputs, plonk_prover_upload_inputs)
     struct Solver {

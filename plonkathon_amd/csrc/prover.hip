@@ -3,7 +3,9 @@
 // Reference behaviour replaced: Prover.prove / round_1..round_5 (/root/reference/prover.py:51-306,
 // spec in SURVEY.md §3.2) for B independent proofs of one circuit run in lock-step, including the
 // Fiat-Shamir transcript (transcript.py:77-123), which runs on the device (32 lanes per proof) so
-// that a whole batch is one uninterrupted stream of kernel launches with no host round trip.
+// that a whole batch is one uninterrupted stream of kernel launches with no host round trip.  A prover over a TABLE of circuits of
+// one group order (plonk_prover_create_multi) labels every proof with its circuit: only the kernels that read the fixed polynomials
+// or the wiring take the label array (null for a table of one, which is plonk_prover_create's prover), the rest never see the circuit.
 //
 // Every committed polynomial is uniquely determined by (circuit, witness, challenges) — the
 // reference adds no blinding (README.md:31-32); PLONK_PROVER_BLINDING adds the PLONK paper's as correction launches beside these
@@ -118,7 +120,8 @@ __global__ void __launch_bounds__(2 * TC_LANES) transcript_kernel(int round, Pro
 //   Z_H by k & 3 (plonk_fr_quotient).  coset_log == log2 n: the lock-step prover's — n4 = 3n points [r][j] = g mu^r w^j, Z(w x)
 //   one place ahead INSIDE the coset, Z_H by r.  The quotient goes to quot[b * out_stride + k].
 struct ZhInv { Fr v[4]; };
-struct QuotientIn { const Fr* wit[5]; const Fr* fixed[FX_COUNT]; const Fr* l0; const Fr* xs; };
+//   A table of circuits (cid != null): proof b reads fixed[k] + cid[b] * fixed_stride.
+struct QuotientIn { const Fr* wit[5]; const Fr* fixed[FX_COUNT]; const Fr* l0; const Fr* xs; const uint32_t* cid; unsigned fixed_stride; };
 // Round 4: the arithmetic runs on lazy limbs (fpl.h) — operands stay unpacked between the 19 products of a point, the gate's
 // four products share two reductions (fpl_mul_add), sums of two are multiplied as they stand and only the seven sums of three
 // or more are carry-swept: ~4 800 instructions per point against ~5 800 on packed residues.  Bounds, in units of m, beside
@@ -133,6 +136,7 @@ __global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, 
             alpha = fpl_from_fp_uniform(st ? st[b].alpha : direct.alpha);                                   // n, [0, 1)
     const L one = fpl_one<FrParams>();
     const size_t row = (size_t)b * n4;
+    const size_t fx = in.cid ? (size_t)in.cid[b] * in.fixed_stride : 0;  // the proof's circuit: the same for the block, like the challenges
     for (unsigned k = blockIdx.x * blockDim.x + threadIdx.x; k < n4; k += gridDim.x * blockDim.x) {
         const unsigned cr = coset_log ? k >> coset_log : 0u, cmask = coset_log ? (1u << coset_log) - 1u : 0u;
         const unsigned kw = coset_log ? ((k & ~cmask) | ((k + 1) & cmask))            // the next point of the same coset
@@ -140,10 +144,10 @@ __global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, 
         const auto ld = [&](const Fr* p) PLONK_LAMBDA_INLINE { return fpl_from_fp(fp_load(p)); };          // n, [0, 1)
         const L a = ld(in.wit[0] + row + k), bb = ld(in.wit[1] + row + k), c = ld(in.wit[2] + row + k);
         // gate: A QL + B QR + A B QM + C QO + PI + QC
-        const L t1 = fpl_mul_add(a, ld(in.fixed[FX_QL] + k), bb, ld(in.fixed[FX_QR] + k));               // n, (-1, 2)
+        const L t1 = fpl_mul_add(a, ld(in.fixed[FX_QL] + fx + k), bb, ld(in.fixed[FX_QR] + fx + k));               // n, (-1, 2)
         const L ab = fpl_mul(a, bb);                                                                       // n, (-1, 2)
-        const L t2 = fpl_mul_add(ab, ld(in.fixed[FX_QM] + k), c, ld(in.fixed[FX_QO] + k));               // n, (-1, 2)
-        const L gate = fpl_norm(fpl_add(fpl_add(t1, t2), fpl_add(ld(in.wit[3] + row + k), ld(in.fixed[FX_QC] + k))));  // four terms: limbs < 2^31; n, (-2, 6)
+        const L t2 = fpl_mul_add(ab, ld(in.fixed[FX_QM] + fx + k), c, ld(in.fixed[FX_QO] + fx + k));               // n, (-1, 2)
+        const L gate = fpl_norm(fpl_add(fpl_add(t1, t2), fpl_add(ld(in.wit[3] + row + k), ld(in.fixed[FX_QC] + fx + k))));  // four terms: limbs < 2^31; n, (-2, 6)
         // permutation: (A + g + b x)(B + g + 2 b x)(C + g + 3 b x) Z - (A + g + b S1)(B + g + b S2)(C + g + b S3) Z(w x)
         const L bx = fpl_mul(beta, ld(in.xs + k));                                                         // n, (-1, 2)
         const L u1 = fpl_norm(fpl_add(gamma, bx));                                                         // n, (-1, 3)
@@ -153,11 +157,11 @@ __global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, 
         L p1 = fpl_mul(fpl_add(a, u1), z);                                                                 // (two terms) x n: |.| < 4;  n, (-1, 2)
         p1 = fpl_mul(fpl_add(bb, u2), p1);                                                                 // < 6 x 2
         p1 = fpl_mul(fpl_add(c, u3), p1);                                                                  // < 8 x 2
-        const L v1 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S1] + k))));                     // n, (-1, 3)
+        const L v1 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S1] + fx + k))));                     // n, (-1, 3)
         L p2 = fpl_mul(fpl_add(a, v1), ld(in.wit[4] + row + kw));                                          // < 4 x 1
-        const L v2 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S2] + k))));
+        const L v2 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S2] + fx + k))));
         p2 = fpl_mul(fpl_add(bb, v2), p2);                                                                 // < 4 x 2
-        const L v3 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S3] + k))));
+        const L v3 = fpl_norm(fpl_add(gamma, fpl_mul(beta, ld(in.fixed[FX_S3] + fx + k))));
         p2 = fpl_mul(fpl_add(c, v3), p2);
         // (Z - 1) L0, and the sum under alpha
         const L first = fpl_mul(fpl_sub(z, one), ld(in.l0 + k));                     // difference x n;  n, (-1, 2)
@@ -194,8 +198,9 @@ __global__ void quotient_combine_kernel(Fr* quot, size_t n, size_t stride, size_
 // prover.py:108-116 — the gate identity on H, row by row: A QL + B QR + A B QM + C QO + PI + QC = 0.  flags[b] |= 1 otherwise
 // (status bit 2).  Together with "Z closes to 1" (prover.py:132, status bit 1) this is exactly when the quotient's numerator is
 // divisible by Z_H — the condition the reference re-checks on the quotient's top coefficients (prover.py:205-208), which a
-// quotient interpolated from 3n points no longer has.
-__global__ void gate_check_kernel(const Fr* abc, const Fr* pub, size_t l, const Fr* pi_or_null, const Fr* fixed_lag, size_t n, size_t B, uint32_t* bad) {
+// quotient interpolated from 3n points no longer has.  fixed_lag: [K][8][n], proof b's circuit is cid[b] (cid == null: circuit 0).
+__global__ void gate_check_kernel(const Fr* abc, const Fr* pub, size_t l, const Fr* pi_or_null, const Fr* fixed_lag, const uint32_t* cid, size_t n, size_t B,
+                                  uint32_t* bad) {
     const size_t total = B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n, i = gI - b * n;
@@ -203,10 +208,11 @@ __global__ void gate_check_kernel(const Fr* abc, const Fr* pub, size_t l, const 
         Fr pi = fp_zero<FrParams>();
         if (pi_or_null) pi = fp_load(pi_or_null + gI);
         else if (i < l) pi = fp_neg(fp_load(pub + b * l + i));
-        Fr gate = fp_add(fp_mul(a, fp_load(fixed_lag + FX_QL * n + i)), fp_mul(bb, fp_load(fixed_lag + FX_QR * n + i)));
-        gate = fp_add(gate, fp_mul(fp_mul(a, bb), fp_load(fixed_lag + FX_QM * n + i)));
-        gate = fp_add(gate, fp_mul(c, fp_load(fixed_lag + FX_QO * n + i)));
-        gate = fp_add(gate, fp_add(pi, fp_load(fixed_lag + FX_QC * n + i)));
+        const Fr* fl = cid ? fixed_lag + (size_t)cid[b] * FX_COUNT * n : fixed_lag;  // a lane finds its proof by division: per lane
+        Fr gate = fp_add(fp_mul(a, fp_load(fl + FX_QL * n + i)), fp_mul(bb, fp_load(fl + FX_QR * n + i)));
+        gate = fp_add(gate, fp_mul(fp_mul(a, bb), fp_load(fl + FX_QM * n + i)));
+        gate = fp_add(gate, fp_mul(c, fp_load(fl + FX_QO * n + i)));
+        gate = fp_add(gate, fp_add(pi, fp_load(fl + FX_QC * n + i)));
         if (!fp_is_zero(gate)) atomicOr(&bad[b], 1u);
     }
 }
@@ -258,7 +264,8 @@ __global__ void __launch_bounds__(64) linearisation_weights_kernel(const ProofSt
 
 // (lazy limbs, round 4: the 15 products of a coefficient pair up under 8 reductions — fpl_mul_add — with the weights unpacked
 // once per block into LDS; the sum of the first seven results rides as "1 x sum" in the eighth, which leaves it reduced)
-__global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, const Fr* fixed_coef, const Fr* tcoef,
+// fixed_coef: [K][8][n], the block's proof is of circuit cid[b] (cid == null: circuit 0)
+__global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr* tcoef,
                                                               const LinWeights* weights, unsigned log_n, size_t B,
                                                               Fr* out) {
     typedef FpL<FrParams> L;
@@ -271,6 +278,7 @@ __global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, c
         for (int q = 0; q < 9; q++) WL[threadIdx.x][q] = w.l[q];
     }
     __syncthreads();
+    if (cid) fixed_coef += (size_t)cid[b] * FX_COUNT * n;
     const Fr* vec[15] = {fixed_coef + FX_QM * n, fixed_coef + FX_QL * n, fixed_coef + FX_QR * n, fixed_coef + FX_QO * n,
                          fixed_coef + FX_QC * n, coef + (4 * B + b) * n, fixed_coef + FX_S3 * n, tcoef + b * 4 * n,
                          tcoef + b * 4 * n + n,   tcoef + b * 4 * n + 2 * n, coef + (0 * B + b) * n,
@@ -458,28 +466,41 @@ static int blinders_for_run(plonk_prover* p, size_t B) {
     return PLONK_OK;
 }
 
-static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32, size_t n_public);
+static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, unsigned K, const uint8_t* selectors_le32, const size_t* n_public);
 
-extern "C" {
-
-int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
-                        size_t n_public, plonk_prover** out) {
-    PLONK_REQUIRE(ctx && srs && selectors_le32 && out, PLONK_ERR_ARG, "bad argument");
+// plonk_prover_create (K = 1) and plonk_prover_create_multi: a table of K circuits of group order 2^log_n, selectors [K][8][n]
+static int prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, unsigned K, const uint8_t* selectors_le32, const size_t* n_public, plonk_prover** out) {
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(log_n >= 1 && log_n + 2 <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "group_order 2^%u out of range", log_n);
     const size_t n = (size_t)1 << log_n;
     PLONK_REQUIRE(log_n <= PROVER_MAX_LOG_N, PLONK_ERR_ARG, "the batched prover supports group_order <= %u (got %zu)", 1u << PROVER_MAX_LOG_N, n);
     PLONK_REQUIRE(srs->n_points >= n, PLONK_ERR_ARG, "SRS has %zu powers, group_order is %zu", srs->n_points, n);
-    PLONK_REQUIRE(n_public <= n, PLONK_ERR_ARG, "more public inputs than rows");
+    for (unsigned c = 0; c < K; c++) PLONK_REQUIRE(n_public[c] <= n, PLONK_ERR_ARG, "more public inputs than rows");
     plonk_prover* p = new plonk_prover();
     memset((void*)p, 0, sizeof *p);
-    const int rc = prover_init(p, ctx, srs, log_n, selectors_le32, n_public);
+    const int rc = prover_init(p, ctx, srs, log_n, K, selectors_le32, n_public);
     if (rc != PLONK_OK) {  // a single cleanup path: everything allocated so far goes with the half-built object
         plonk_prover_destroy(p);
         return rc;
     }
     *out = p;
     return PLONK_OK;
+}
+
+extern "C" {
+
+int plonk_prover_create(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
+                        size_t n_public, plonk_prover** out) {
+    PLONK_REQUIRE(ctx && srs && selectors_le32 && out, PLONK_ERR_ARG, "bad argument");
+    return prover_create(ctx, srs, log_n, 1, selectors_le32, &n_public, out);
+}
+
+int plonk_prover_create_multi(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, size_t n_circuits, const uint8_t* selectors_le32, const size_t* n_public,
+                              plonk_prover** out) {
+    PLONK_REQUIRE(ctx && srs && selectors_le32 && n_public && out, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(n_circuits >= 1 && n_circuits <= PLONK_PROVER_MAX_CIRCUITS, PLONK_ERR_ARG, "%zu circuits: a table holds 1 to %d", n_circuits,
+                  PLONK_PROVER_MAX_CIRCUITS);
+    return prover_create(ctx, srs, log_n, (unsigned)n_circuits, selectors_le32, n_public, out);
 }
 
 }  // extern "C"
@@ -492,10 +513,10 @@ static void free_coset_tables(plonk_prover::Circuit& c) {
 static int coset_tables(plonk_prover* p) {
     plonk_prover::Circuit& c = p->circuit;
     plonk_ctx* ctx = c.ctx;
-    const size_t n = c.n, e = sizeof(Fr), n3 = c.qcosets * n;
+    const size_t n = c.n, e = sizeof(Fr), n3 = c.qcosets * n, K = c.n_circuits;
     const unsigned log_n = c.log_n;
     free_coset_tables(c);
-    PLONK_TRY(dev_alloc((void**)&c.fixed_big, 8 * n3 * e));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_big, K * 8 * n3 * e));
     PLONK_TRY(dev_alloc((void**)&c.l0_big, n3 * e));
     PLONK_TRY(dev_alloc((void**)&c.x_big, n3 * e));
     PLONK_TRY(dev_alloc((void**)&c.g_pow, n3 * e));
@@ -511,7 +532,7 @@ static int coset_tables(plonk_prover* p) {
     }
     // the circuit polynomials' values on the cosets: P(g mu^r w^j) is the size-n transform of c_i (g mu^r)^i
     const NttFan fan{c.qcosets, 0u, (unsigned)n, (unsigned)n};
-    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8, n, n, n3, c.g_pow, nullptr, false, &fan));
+    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8 * K, n, n, n3, c.g_pow, nullptr, false, &fan));  // [K][8][qcosets][n]
     // L0: Lagrange vector e_0 has coefficient form (1/n, 1/n, ...)          prover.py:184-186
     void* tmpv;
     PLONK_TRY(ctx_scratch(ctx, 2, n * e, &tmpv));  // context-owned scratch: nothing to leak on an error path
@@ -558,14 +579,22 @@ static int set_blinding(plonk_prover* p, bool on) {
     return PLONK_OK;
 }
 
-static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, const uint8_t* selectors_le32,
-                       size_t n_public) {
+static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, unsigned K, const uint8_t* selectors_le32,
+                       const size_t* n_public_of) {
     const size_t n = (size_t)1 << log_n;
     plonk_prover::Circuit& c = p->circuit;
     c.ctx = ctx;
     c.srs = srs;
     c.log_n = log_n;
     c.n = n;
+    c.n_circuits = K;
+    c.n_public_of = (size_t*)malloc(K * sizeof(size_t));
+    PLONK_REQUIRE(c.n_public_of, PLONK_ERR_NOMEM, "out of host memory");
+    size_t n_public = 0;  // l_max: the public rows, sparse PI and li_big are sized by the widest circuit, zeros beyond a circuit's own
+    for (unsigned k = 0; k < K; k++) {
+        c.n_public_of[k] = n_public_of[k];
+        if (n_public_of[k] > n_public) n_public = n_public_of[k];
+    }
     c.n_public = n_public;
     c.chal = challenge_consts();
     c.g = host_fr_u64(5);  // multiplicative generator (curve.py:5): g^(4n) != 1, so Z_H != 0 on the coset
@@ -573,13 +602,13 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
     c.n_inv = fp_inv(host_fr_u64((uint64_t)n));
     c.half = fp_inv(host_fr_u64(2));
     const size_t e = sizeof(Fr);
-    PLONK_TRY(dev_alloc((void**)&c.fixed_lag, 8 * n * e));
-    PLONK_TRY(dev_alloc((void**)&c.fixed_coef, 8 * n * e));
-    PLONK_TRY(plonk_fr_upload(ctx, c.fixed_lag, selectors_le32, 8 * n));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_lag, K * 8 * n * e));
+    PLONK_TRY(dev_alloc((void**)&c.fixed_coef, K * 8 * n * e));
+    PLONK_TRY(plonk_fr_upload(ctx, c.fixed_lag, selectors_le32, K * 8 * n));
     PLONK_TRY(intake_init(p, selectors_le32));
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &c.roots));
     // coefficient forms of the 8 circuit polynomials
-    PLONK_TRY(ntt_run(ctx, c.fixed_lag, c.fixed_coef, log_n, true, 8, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(ntt_run(ctx, c.fixed_lag, c.fixed_coef, log_n, true, 8 * K, n, n, n, nullptr, nullptr, true));
     // Z_H on coset r is the constant (g mu^r)^n - 1 = g^n i^r - 1, i = mu^n            prover.py:178
     const Fr one = fp_one<FrParams>();
     Fr gn = c.g;
@@ -632,6 +661,7 @@ int plonk_prover_destroy(plonk_prover* p) {
     free_coset_tables(c);
     dev_free_all({(void**)&c.fixed_lag, (void**)&c.fixed_coef, (void**)&p->blinding_src.htab, (void**)&p->blinding_src.explicit_b});
     intake_destroy(p);
+    free(c.n_public_of);
     delete p;
     return PLONK_OK;
 }
@@ -656,12 +686,13 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     const bool blind = p->blinding;            // every `if (blind)` below is a correction of prover_blind.h behind the step it follows
     BlindState* bs = r.blind;
     if (blind) PLONK_TRY(blinders_for_run(p, B));
+    const uint32_t* cid = c.n_circuits > 1 ? p->labels.dev : nullptr;  // the proofs' circuits (a table of one: circuit 0, no array)
 
     transcript_round(p, B, 0);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
     PLONK_CHECK_HIP(hipMemsetAsync(r.closes + B, 0, B * sizeof(uint32_t), s));
     PLONK_LAUNCH(gate_check_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)r.wit_lag, pub, c.n_public,
-                 c.sparse_pi ? (const Fr*)nullptr : (const Fr*)(r.wit_lag + 3 * B * n), (const Fr*)c.fixed_lag, n, B, r.closes + B);  // prover.py:108-116
+                 c.sparse_pi ? (const Fr*)nullptr : (const Fr*)(r.wit_lag + 3 * B * n), (const Fr*)c.fixed_lag, cid, n, B, r.closes + B);  // prover.py:108-116
     if (c.sparse_pi) {
         PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 3 * B, n, n, n, nullptr, nullptr, true));
         if (c.n_public) PLONK_LAUNCH(pi_coeffs_kernel, grid1(B * n), dim3(256), 0, s, pub, c.n_public, c.roots_inv, n, B, c.n_inv, r.coef + 3 * B * n);
@@ -673,11 +704,13 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     if (blind) blind_commit(p, B, 0, 3);
     transcript_round(p, B, 1);
     // ---- round 2: grand product Z, commit                                      prover.py:121-152
-    GrandProductIn gp;
+    GrandProductIn gp = {};
     for (int k = 0; k < 3; k++) {
         gp.abc[k] = r.wit_lag + (size_t)k * B * n;
         gp.sig[k] = c.fixed_lag + (FX_S1 + k) * n;
     }
+    gp.cid = cid;
+    gp.sig_stride = FX_COUNT * n;
     // (the three scan families are instrumented for plonk_profile_read: tools/prover_scale.py)
     PLONK_TRY(prof_begin(ctx, "prover_grand_product", 11.0 * 32.0 * (double)n * (double)B));
     PLONK_TRY(scan_grand_product(s, S, gp, c.roots, state, RoundChallenges{}, n, B, r.z_lag, r.closes, r.num, r.wz, r.seg));  // num / wz: scratch until round 5
@@ -709,11 +742,13 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     }
     ZhInv zh;
     for (int k = 0; k < 4; k++) zh.v[k] = c.zh_inv[k < (int)c.qcosets ? k : 0];
-    QuotientIn qi;
+    QuotientIn qi = {};
     for (int k = 0; k < 5; k++) qi.wit[k] = r.big + (size_t)k * B * n3;
     for (int k = 0; k < FX_COUNT; k++) qi.fixed[k] = c.fixed_big + (size_t)k * n3;
     qi.l0 = c.l0_big;
     qi.xs = c.x_big;
+    qi.cid = cid;
+    qi.fixed_stride = (unsigned)(FX_COUNT * n3);
     PLONK_LAUNCH(quotient_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)B), dim3(256), 0, s, qi, zh, (const ProofState*)state, RoundChallenges{},
                  (unsigned)n3, r.quot, log_n, (unsigned)n4);
     const NttFan slices{c.qcosets, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
@@ -730,14 +765,14 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     transcript_round(p, B, 3);
     // ---- round 4: evaluations                                                  prover.py:228-239
     PLONK_TRY(prof_begin(ctx, "prover_evaluations", 7.0 * 32.0 * (double)n * (double)B));
-    PLONK_TRY(scan_evaluations(s, S, r.coef, c.fixed_coef, c.w, state, n, B, r.seg));
+    PLONK_TRY(scan_evaluations(s, S, r.coef, c.fixed_coef, cid, c.w, state, n, B, r.seg));
     PLONK_TRY(prof_end(ctx));
     if (blind) PLONK_LAUNCH(blind_evals_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const BlindState*)bs, state, c.w, log_n, B);
     transcript_round(p, B, 4);
     // ---- round 5: opening polynomials in coefficient form, commit              prover.py:241-306
     PLONK_LAUNCH(linearisation_weights_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const ProofState*)state, log_n, c.n_inv, B, r.lin_w);
     PLONK_LAUNCH(linearisation_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, (const Fr*)r.coef, (const Fr*)c.fixed_coef,
-                 (const Fr*)r.quot, (const LinWeights*)r.lin_w, log_n, B, r.num);
+                 cid, (const Fr*)r.quot, (const LinWeights*)r.lin_w, log_n, B, r.num);
     if (blind) PLONK_LAUNCH(blind_openings_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, bs, (const ProofState*)state, (const Fr*)r.lin_w, c.w, B);
     PLONK_TRY(prof_begin(ctx, "prover_divisions", 2.0 * 3.0 * 32.0 * (double)n * (double)B));
     const DivideIn dv = {{r.num, r.coef + 4 * B * n}, {r.wz, r.wz + B * n}};  // W_z's numerator by X - zeta, Z by X - zeta w
@@ -874,7 +909,7 @@ int plonk_fr_quotient(plonk_ctx* ctx, unsigned log_n, const void* const d_evals[
                       le32_below_modulus(gamma_le32, false), PLONK_ERR_ARG, "offset / challenge is not a canonical Fr value");
     const size_t n4 = (size_t)4 << log_n;
     const Fr off = fr_from_le32(offset_le32), one = fp_one<FrParams>();
-    QuotientIn qi;
+    QuotientIn qi = {};  // no circuit labels: the fourteen vectors are the caller's
     for (int k = 0; k < 5; k++) qi.wit[k] = (const Fr*)d_evals[k];
     qi.fixed[FX_QL] = (const Fr*)d_evals[5];
     qi.fixed[FX_QR] = (const Fr*)d_evals[6];

@@ -18,6 +18,8 @@
 //            (the levelised form, solve_form_of: witness_solve_levels_kernel in that kernel's place)
 //   GATHER = witness_scatter_kernel · public_gather_kernel (if n_public) · PI column · record vars.read
 //   PI column = memset (n_public == 0) | pi_fill_kernel (dense PI) | nothing (sparse PI: round 1 builds it from pub)
+// A prover over a table of circuits (plonk_prover_create_multi): every upload above first takes the labels plonk_prover_set_labels left
+// for it — C: H2D labels (behind an event: the host copy is not rewritten under it) — and the gathers index the wiring tables with them.
 // The solver writes `vars` in place: on C it is behind the previous batch's gathers, the only readers, so only the staging buffer
 // that H writes needs its `read` event.  An async path's canonical-range verdict comes back as PROVER_ST_BAD_INPUT of the download.
 //
@@ -55,20 +57,23 @@ __global__ void pi_fill_kernel(const Fr* pub, size_t n_public, size_t n, size_t 
 }
 
 // prover.py:94-103 on the device: A[i], B[i], C[i] = witness[wires[i].L / R / O], witness[None] = 0, zero padded to n.
-// vars = [B][V] variable values; cell[3][n] = variable index of each wire cell (V: empty); out = wit_lag [3][B][n].
-__global__ void witness_scatter_kernel(const Fr* vars, const uint32_t* cell, size_t V, size_t n, size_t B, Fr* out) {
+// vars = [B][V] variable values; cell[K][3][n] = variable index of each wire cell (V: empty); out = wit_lag [3][B][n].  Proof b is
+// wired as circuit cid[b] (cid == null: circuit 0), its variables numbered in that circuit's order.
+__global__ void witness_scatter_kernel(const Fr* vars, const uint32_t* cell, const uint32_t* cid, size_t V, size_t n, size_t B, Fr* out) {
     const size_t total = 3 * B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t j = gI / (B * n), r = gI - j * B * n, b = r / n, i = r - b * n;
-        const uint32_t idx = cell[j * n + i];
+        const uint32_t idx = cell[(cid ? (size_t)cid[b] * 3 * n : 0) + j * n + i];
         fp_store(out + gI, idx < V ? fp_load(vars + b * V + idx) : fp_zero<FrParams>());
     }
 }
-__global__ void public_gather_kernel(const Fr* vars, const uint32_t* pub_index, size_t V, size_t l, size_t B, Fr* pub) {
+// pub_index[K][l]; an entry V pads the row of a circuit with fewer than l public inputs: the value is 0
+__global__ void public_gather_kernel(const Fr* vars, const uint32_t* pub_index, const uint32_t* cid, size_t V, size_t l, size_t B, Fr* pub) {
     const size_t total = B * l;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / l, k = gI - b * l;
-        fp_store(pub + gI, fp_load(vars + b * V + pub_index[k]));
+        const uint32_t idx = pub_index[(cid ? (size_t)cid[b] * l : 0) + k];
+        fp_store(pub + gI, idx < V ? fp_load(vars + b * V + idx) : fp_zero<FrParams>());
     }
 }
 
@@ -82,7 +87,10 @@ static int intake_init(plonk_prover* p, const uint8_t* selectors_le32) {
 static void intake_destroy(plonk_prover* p) {
     dev_free_all({(void**)&p->intake.vars.buf, (void**)&p->intake.inputs.buf, (void**)&p->intake.bad_input, (void**)&p->wiring.cell_index,
                   (void**)&p->wiring.pub_index, (void**)&p->solver.desc, (void**)&p->solver.order, (void**)&p->solver.level_start,
-                  (void**)&p->solver.input_index, (void**)&p->solver.bad});
+                  (void**)&p->solver.input_index, (void**)&p->solver.bad, (void**)&p->labels.dev});
+    free(p->labels.pending);
+    free(p->labels.host);
+    if (p->labels.copied) hipEventDestroy(p->labels.copied);
     StagedSlot& sl = p->staged;  // a batch still staged goes with its buffers (plonk_prover_destroy has waited for both streams)
     dev_free_all({(void**)&sl.wit_lag, (void**)&sl.pub, (void**)&sl.vars.buf, (void**)&sl.inputs.buf, (void**)&sl.bad_input, (void**)&sl.solve_bad});
     for (hipEvent_t ev : {p->intake.vars.read, p->intake.inputs.read, p->intake.ev_copied, sl.vars.read, sl.inputs.read, sl.ready, sl.released})
@@ -104,6 +112,46 @@ static int staging_copy(plonk_prover* p, Staging* st, const uint8_t* src, size_t
     PLONK_CHECK_HIP(hipMemcpyAsync(st->buf, src, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
     PLONK_CHECK_HIP(hipEventRecord(p->intake.ev_copied, ctx->copy_stream));
     PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, p->intake.ev_copied, 0));
+    return PLONK_OK;
+}
+
+// What a prover over a table of K > 1 circuits does not do yet: the solver's plan and the staged slot are per circuit.
+#define PLONK_REQUIRE_ONE_CIRCUIT(p, what) \
+    PLONK_REQUIRE((p)->circuit.n_circuits == 1, PLONK_ERR_STATE, what ": not on a prover over a table of %u circuits", (p)->circuit.n_circuits)
+
+// The labels an upload of B proofs will take (plonk_prover_set_labels).  labels_check changes nothing; labels_commit makes them the
+// resident batch's: the host copy, and for a table of more than one circuit the device array behind everything on stream s.
+static int labels_check(const plonk_prover* p, size_t B) {
+    const plonk_prover::Labels& lb = p->labels;
+    PLONK_REQUIRE(!lb.pending_batch || lb.pending_batch == B, PLONK_ERR_STATE, "upload: batch %zu, but the labels were set for a batch of %zu", B,
+                  lb.pending_batch);
+    PLONK_REQUIRE(lb.pending_batch || p->circuit.n_circuits == 1, PLONK_ERR_STATE,
+                  "upload: a table of %u circuits, and plonk_prover_set_labels has not named the circuit of each of the %zu proofs", p->circuit.n_circuits, B);
+    return PLONK_OK;
+}
+static int labels_commit(plonk_prover* p, size_t B, hipStream_t s, bool take_pending = true) {
+    plonk_prover::Labels& lb = p->labels;
+    if (lb.copy_pending) PLONK_CHECK_HIP(hipEventSynchronize(lb.copied));  // the previous batch's copy still reads `host`
+    lb.copy_pending = false;
+    if (B > lb.host_cap) {
+        free(lb.host);
+        lb.host_cap = 0;
+        lb.host = (uint32_t*)malloc(B * sizeof(uint32_t));
+        PLONK_REQUIRE(lb.host, PLONK_ERR_NOMEM, "out of host memory");
+        lb.host_cap = B;
+    }
+    if (take_pending && lb.pending_batch) {  // (labels_check: they are of B proofs)
+        memcpy(lb.host, lb.pending, B * sizeof(uint32_t));
+        lb.pending_batch = 0;
+    } else {
+        memset(lb.host, 0, B * sizeof(uint32_t));
+    }
+    if (p->circuit.n_circuits == 1) return PLONK_OK;  // every kernel is given a null array
+    PLONK_TRY(dev_grow(s, &lb.cap, B, {{(void**)&lb.dev, B * sizeof(uint32_t)}}));
+    if (!lb.copied) PLONK_CHECK_HIP(hipEventCreate(&lb.copied));
+    PLONK_CHECK_HIP(hipMemcpyAsync(lb.dev, lb.host, B * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    PLONK_CHECK_HIP(hipEventRecord(lb.copied, s));
+    lb.copy_pending = true;
     return PLONK_OK;
 }
 
@@ -151,8 +199,9 @@ static void enqueue_solve(plonk_prover* p, const BatchSet& bs, size_t B, hipStre
 }
 static int enqueue_gather(plonk_prover* p, const BatchSet& bs, size_t B, hipStream_t s) {
     const size_t n = p->circuit.n, l = p->circuit.n_public, V = p->wiring.n_vars;
-    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.cell_index, V, n, B, bs.wit_lag);
-    if (l) PLONK_LAUNCH(public_gather_kernel, grid1(B * l), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.pub_index, V, l, B, bs.pub);
+    const uint32_t* cid = p->circuit.n_circuits > 1 ? p->labels.dev : nullptr;  // (a staged set is a one-circuit prover's)
+    PLONK_LAUNCH(witness_scatter_kernel, grid1(3 * B * n), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.cell_index, cid, V, n, B, bs.wit_lag);
+    if (l) PLONK_LAUNCH(public_gather_kernel, grid1(B * l), dim3(256), 0, s, (const Fr*)bs.vars, (const uint32_t*)p->wiring.pub_index, cid, V, l, B, bs.pub);
     return fill_pi_column(p, bs.wit_lag, bs.pub, B, s);
 }
 
@@ -166,7 +215,9 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(p->wiring.n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
+    if (from_inputs) PLONK_REQUIRE_ONE_CIRCUIT(p, "upload_inputs");
     PLONK_REQUIRE(p->solver.n_inputs || !from_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
+    PLONK_TRY(labels_check(p, B));
     PLONK_TRY(ensure_batch(p, B));
     plonk_prover::Intake& in = p->intake;
     hipStream_t s = ctx->stream;
@@ -180,6 +231,7 @@ static int prover_upload(plonk_prover* p, const uint8_t* src_le32, size_t B, boo
     in.resident_b = 0;
     in.vars_valid = p->solver.valid = false;
     in.bad_stride = from_inputs ? K : V;
+    PLONK_TRY(labels_commit(p, B, s));
     // convert: `vars` of the batch in Montgomery form, and the verdict on the uploaded values in *bad_input
     if (from_inputs) {
         PLONK_TRY(staging_copy(p, &in.inputs, src_le32, B * K * sizeof(Fr), async));
@@ -241,6 +293,7 @@ static int prover_stage(plonk_prover* p, const uint8_t* src_le32, size_t B, bool
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
     StagedSlot& sl = p->staged;
+    PLONK_REQUIRE_ONE_CIRCUIT(p, "stage");
     PLONK_REQUIRE(p->wiring.n_vars, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
     PLONK_REQUIRE(p->solver.n_inputs || !from_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
     PLONK_REQUIRE(!sl.batch, PLONK_ERR_STATE, "stage: a batch of %zu is already staged (plonk_prover_advance takes it)", sl.batch);
@@ -291,7 +344,9 @@ int plonk_prover_advance(plonk_prover* p, size_t* out_batch) {
     PLONK_ENTER(ctx);
     StagedSlot& sl = p->staged;
     plonk_prover::Intake& in = p->intake;
+    PLONK_REQUIRE_ONE_CIRCUIT(p, "advance");
     PLONK_REQUIRE(sl.batch, PLONK_ERR_STATE, "advance: no batch is staged");
+    PLONK_TRY(labels_commit(p, sl.batch, ctx->stream, false));  // a staged batch takes no labels: circuit 0 (pending ones wait for an upload)
     const size_t B = sl.batch;
     PLONK_TRY(ensure_rounds(p, B));  // a staged batch larger than any before: the rounds' own buffers grow here, behind the outgoing batch
     PLONK_CHECK_HIP(hipStreamWaitEvent(ctx->stream, sl.ready, 0));
@@ -318,7 +373,16 @@ int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const 
     PLONK_REQUIRE(p && abc_le32 && B && (public_le32 || !p->circuit.n_public), PLONK_ERR_ARG, "bad argument");
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
+    PLONK_TRY(labels_check(p, B));
+    // a public row is [n_public] of the widest circuit: beyond its own circuit's count it must be zero, or PI would not be the circuit's
+    const size_t l_max = p->circuit.n_public;
+    for (size_t b = 0; b < B && p->labels.pending_batch; b++)
+        for (size_t k = 32 * (b * l_max + p->circuit.n_public_of[p->labels.pending[b]]); k < 32 * (b + 1) * l_max; k++)
+            PLONK_REQUIRE(!public_le32[k], PLONK_ERR_ARG, "proof %zu: public value %zu is not zero, and circuit %u has %zu public inputs", b,
+                          k / 32 - b * l_max, p->labels.pending[b], p->circuit.n_public_of[p->labels.pending[b]]);
     PLONK_TRY(ensure_batch(p, B));
+    p->intake.resident_b = 0;
+    PLONK_TRY(labels_commit(p, B, ctx->stream));
     if (p->intake.bad_input) PLONK_CHECK_HIP(hipMemsetAsync(p->intake.bad_input, 0xff, sizeof(unsigned long long), ctx->stream));
     PLONK_TRY(plonk_fr_upload(ctx, p->rounds.wit_lag, abc_le32, 3 * B * p->circuit.n));
     if (p->circuit.n_public) PLONK_TRY(plonk_fr_upload(ctx, p->intake.pub, public_le32, B * p->circuit.n_public));
@@ -331,17 +395,24 @@ int plonk_prover_upload_witness(plonk_prover* p, const uint8_t* abc_le32, const 
 
 // cell_index[3][n]: variable index carried by each wire cell (column L/R/O, row), n_vars for an empty cell or a
 // padding row; public_index[n_public]: the public variables, in the order of the public rows (prover.py:57-62).
-int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars) {
+// plonk_prover_set_wiring_multi: the same for every circuit of the table, cell_index[K][3][n] and public_index[K][n_public] with
+// n_public the widest circuit's: a circuit's row holds its own public variables, then n_vars as the padding entry.  One n_vars
+// serves the table; every circuit's variables are numbered in its own order.
+int plonk_prover_set_wiring_multi(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars) {
     PLONK_REQUIRE(p && cell_index && n_vars && (public_index || !p->circuit.n_public), PLONK_ERR_ARG, "bad argument");
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(!p->staged.batch, PLONK_ERR_STATE, "set_wiring: a batch of %zu is staged under the wiring in force", p->staged.batch);
     plonk_prover::Wiring& w = p->wiring;
-    const size_t cells = 3 * p->circuit.n, l = p->circuit.n_public;
+    const size_t K = p->circuit.n_circuits, cells = K * 3 * p->circuit.n, l_max = p->circuit.n_public, l = K * l_max;
     for (size_t k = 0; k < cells; k++)
         PLONK_REQUIRE(cell_index[k] <= n_vars, PLONK_ERR_ARG, "wire cell %zu names variable %u of %zu", k, cell_index[k], n_vars);
-    for (size_t k = 0; k < l; k++)
-        PLONK_REQUIRE(public_index[k] < n_vars, PLONK_ERR_ARG, "public input %zu names variable %u of %zu", k, public_index[k], n_vars);
+    for (size_t k = 0; k < l; k++) {
+        const bool own = k % l_max < p->circuit.n_public_of[k / l_max];
+        PLONK_REQUIRE(!own || public_index[k] < n_vars, PLONK_ERR_ARG, "public input %zu names variable %u of %zu", k, public_index[k], n_vars);
+        PLONK_REQUIRE(own || public_index[k] == n_vars, PLONK_ERR_ARG, "public entry %zu pads its circuit's row: %u is not the marker %zu", k,
+                      public_index[k], n_vars);
+    }
     if (!w.cell_index) PLONK_TRY(dev_alloc((void**)&w.cell_index, cells * sizeof(uint32_t)));
     if (!w.pub_index) PLONK_TRY(dev_alloc((void**)&w.pub_index, (l + 1) * sizeof(uint32_t)));
     PLONK_CHECK_HIP(hipMemcpyAsync(w.cell_index, cell_index, cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -357,6 +428,28 @@ int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const u
     return PLONK_OK;
 }
 
+int plonk_prover_set_wiring(plonk_prover* p, const uint32_t* cell_index, const uint32_t* public_index, size_t n_vars) {
+    PLONK_REQUIRE(p, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(p->circuit.n_circuits == 1, PLONK_ERR_STATE, "a prover over a table of %u circuits is wired with plonk_prover_set_wiring_multi",
+                  p->circuit.n_circuits);
+    return plonk_prover_set_wiring_multi(p, cell_index, public_index, n_vars);
+}
+
+// The circuit of each proof of the NEXT upload, which must be of `batch` proofs: circuit[b] < the table's K.  They serve that one
+// upload, as plonk_prover_set_blinders serves the next run, and stay with the batch it makes resident.
+int plonk_prover_set_labels(plonk_prover* p, const uint32_t* circuit, size_t batch) {
+    PLONK_REQUIRE(p && circuit && batch, PLONK_ERR_ARG, "bad argument");
+    for (size_t b = 0; b < batch; b++)
+        PLONK_REQUIRE(circuit[b] < p->circuit.n_circuits, PLONK_ERR_ARG, "proof %zu: circuit %u of a table of %u", b, circuit[b], p->circuit.n_circuits);
+    plonk_prover::Labels& lb = p->labels;
+    uint32_t* mem = (uint32_t*)realloc(lb.pending, batch * sizeof(uint32_t));
+    PLONK_REQUIRE(mem, PLONK_ERR_NOMEM, "out of host memory");
+    lb.pending = mem;
+    memcpy(lb.pending, circuit, batch * sizeof(uint32_t));
+    lb.pending_batch = batch;
+    return PLONK_OK;
+}
+
 int plonk_prover_upload_variables(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload(p, vars_le32, B, false, false); }
 int plonk_prover_upload_variables_async(plonk_prover* p, const uint8_t* vars_le32, size_t B) { return prover_upload(p, vars_le32, B, false, true); }
 
@@ -368,6 +461,7 @@ int plonk_prover_set_inputs(plonk_prover* p, const uint32_t* input_index, size_t
     *out_missing_var = SOLVE_NO_VARIABLE;
     plonk_ctx* ctx = p->circuit.ctx;
     PLONK_ENTER(ctx);
+    PLONK_REQUIRE_ONE_CIRCUIT(p, "set_inputs");
     PLONK_REQUIRE(p->wiring.n_vars && p->wiring.cell_host, PLONK_ERR_STATE, "plonk_prover_set_wiring has not been called");
     PLONK_REQUIRE(!p->staged.batch, PLONK_ERR_STATE, "set_inputs: a batch of %zu is staged under the plan in force", p->staged.batch);
     plonk_prover::Solver& sv = p->solver;
@@ -452,6 +546,7 @@ int plonk_prover_solve_plan(plonk_prover* p, size_t batch, uint32_t out[7]) {
     PLONK_REQUIRE(p && batch && out, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(p->circuit.ctx);
     const plonk_prover::Solver& sv = p->solver;
+    PLONK_REQUIRE_ONE_CIRCUIT(p, "solve_plan");
     PLONK_REQUIRE(sv.n_inputs, PLONK_ERR_STATE, "plonk_prover_set_inputs has not been called");
     const uint32_t plan[7] = {sv.rows, sv.active, sv.levels, sv.widest, sv.threads,
                               solve_plan_form(device_cus(p->circuit.ctx->device), sv.active, sv.steps, sv.threads, batch), sv.steps};

@@ -40,7 +40,8 @@ PLONK_DEV LaneRange seg_lane_range(size_t n, unsigned S, unsigned seg, unsigned 
 // in the scans and zeroes the ratio it belongs to (py_ecc: x / 0 == 0).
 // Inputs by pointer: proof b's columns at abc[k] + b n, the permutation polynomials sig[k] shared.  The challenges come
 // from the proofs' transcript states (st, the lock-step prover) or, st == null, from `direct` (plonk_fr_grand_product).
-struct GrandProductIn { const Fr* abc[3]; const Fr* sig[3]; };
+// A table of circuits (cid != null): proof b's permutation polynomials are sig[k] + cid[b] * sig_stride.
+struct GrandProductIn { const Fr* abc[3]; const Fr* sig[3]; const uint32_t* cid; size_t sig_stride; };
 struct GpProducts { Fr n, d; };
 
 // The factors of proof b's rows [r.lo, r.hi), once, into NUM / DEN (this proof's; a lane only ever touches its own chunk); the
@@ -48,7 +49,8 @@ struct GpProducts { Fr n, d; };
 PLONK_DEV GpProducts gp_chunk_factors(const GrandProductIn& in, const Fr* roots, const Fr& beta, const Fr& gamma, size_t b, size_t n,
                                       const LaneRange& r, Fr* NUM, Fr* DEN) {
     const Fr *A = in.abc[0] + b * n, *Bv = in.abc[1] + b * n, *C = in.abc[2] + b * n;
-    const Fr *S1 = in.sig[0], *S2 = in.sig[1], *S3 = in.sig[2];
+    const size_t so = in.cid ? (size_t)in.cid[b] * in.sig_stride : 0;
+    const Fr *S1 = in.sig[0] + so, *S2 = in.sig[1] + so, *S3 = in.sig[2] + so;
     const Fr one = fp_one<FrParams>();
     GpProducts p = {one, one};
     for (size_t i = r.lo; i < r.hi; i++) {
@@ -128,9 +130,11 @@ __global__ void __launch_bounds__(SCAN_THREADS) grand_product_kernel(GrandProduc
 // ------------------------------------------------------------------------------------------------
 // Round 4 (prover.py:228-239): evaluate coefficient forms at zeta (and Z at zeta*w): lane t Horner-evaluates its chunk of each
 // polynomial, scales by x^(chunk start) and the workgroup tree-reduces.  polys: Ac, Bc, Cc, S1c, S2c at zeta; Zc at zeta*w; PIc
-// at zeta.  Leaves the seven sums over the workgroup's rows in red[p][0].
-PLONK_DEV void eval_chunk_sums(Fr (*red)[SCAN_THREADS], const Fr* coef, const Fr* fixed_coef, const Fr& zeta, const Fr& zeta_w, size_t b,
-                               size_t n, size_t B, const LaneRange& r, unsigned tid) {
+// at zeta.  Leaves the seven sums over the workgroup's rows in red[p][0].  fixed_coef: [K][8][n], proof b is of circuit cid[b]
+// (cid == null: circuit 0).
+PLONK_DEV void eval_chunk_sums(Fr (*red)[SCAN_THREADS], const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr& zeta, const Fr& zeta_w,
+                               size_t b, size_t n, size_t B, const LaneRange& r, unsigned tid) {
+    if (cid) fixed_coef += (size_t)cid[b] * FX_COUNT * n;
     const Fr* polys[NEVAL] = {coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
                               fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (4 * B + b) * n,
                               coef + (3 * B + b) * n};
@@ -162,13 +166,13 @@ PLONK_DEV void eval_chunk_sums(Fr (*red)[SCAN_THREADS], const Fr* coef, const Fr
 }
 
 // One workgroup per proof.
-__global__ void __launch_bounds__(SCAN_THREADS) eval_kernel(const Fr* coef, const Fr* fixed_coef, Fr w, ProofState* st,
+__global__ void __launch_bounds__(SCAN_THREADS) eval_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, ProofState* st,
                                                             size_t n, size_t B) {
     __shared__ Fr red[NEVAL][SCAN_THREADS];
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x;
     const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    eval_chunk_sums(red, coef, fixed_coef, zeta, zeta_w, b, n, B, block_lane_range(n, tid), tid);
+    eval_chunk_sums(red, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, block_lane_range(n, tid), tid);
     if (tid < NEVAL) st[b].evals[tid] = red[tid][0];
 }
 
@@ -305,13 +309,13 @@ __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_apply_kernel(size_t n, co
 
 // Evaluations, launch 1 of 2, grid (S, B): the blocked Horner over the segment's rows, every lane's chains scaled by x^(global
 // chunk start); the segment's seven sums go to part[b][s][NEVAL].
-__global__ void __launch_bounds__(SCAN_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, Fr w, const ProofState* st,
+__global__ void __launch_bounds__(SCAN_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, const ProofState* st,
                                                                 size_t n, size_t B, Fr* part) {
     __shared__ Fr red[NEVAL][SCAN_THREADS];
     const size_t b = blockIdx.y;
     const unsigned tid = threadIdx.x, S = gridDim.x;
     const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    eval_chunk_sums(red, coef, fixed_coef, zeta, zeta_w, b, n, B, seg_lane_range(n, S, blockIdx.x, tid), tid);
+    eval_chunk_sums(red, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, seg_lane_range(n, S, blockIdx.x, tid), tid);
     if (tid < NEVAL) fp_store(part + (b * S + blockIdx.x) * NEVAL + tid, red[tid][0]);
 }
 
@@ -469,14 +473,14 @@ static int scan_grand_product(hipStream_t s, unsigned S, const GrandProductIn& g
     return PLONK_OK;
 }
 
-static int scan_evaluations(hipStream_t s, unsigned S, const Fr* coef, const Fr* fixed_coef, const Fr& w, ProofState* st, size_t n,
-                            size_t B, Fr* seg) {
+static int scan_evaluations(hipStream_t s, unsigned S, const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr& w, ProofState* st,
+                            size_t n, size_t B, Fr* seg) {
     if (S == 1) {
-        PLONK_LAUNCH(eval_kernel, dim3((unsigned)B), dim3(SCAN_THREADS), 0, s, coef, fixed_coef, w, st, n, B);
+        PLONK_LAUNCH(eval_kernel, dim3((unsigned)B), dim3(SCAN_THREADS), 0, s, coef, fixed_coef, cid, w, st, n, B);
         return PLONK_OK;
     }
     Fr* part = scan_scratch_parts(seg, B, S).eval_part;
-    PLONK_LAUNCH(eval_seg_kernel, dim3(S, (unsigned)B), dim3(SCAN_THREADS), 0, s, coef, fixed_coef, w, (const ProofState*)st, n, B, part);
+    PLONK_LAUNCH(eval_seg_kernel, dim3(S, (unsigned)B), dim3(SCAN_THREADS), 0, s, coef, fixed_coef, cid, w, (const ProofState*)st, n, B, part);
     PLONK_LAUNCH(eval_seg_finish_kernel, dim3((unsigned)B), dim3(SCAN_THREADS), 0, s, (const Fr*)part, S, st);
     return PLONK_OK;
 }

@@ -719,6 +719,7 @@ int plonk_verifier_load_prover(plonk_verifier* v, plonk_prover* p, size_t batch,
     PLONK_REQUIRE(v && p && batch && seed, PLONK_ERR_ARG, "bad argument");
     PLONK_REQUIRE(v->n_circuits == 1, PLONK_ERR_STATE, "a verifier of %u circuits loads with plonk_verifier_load_provers", v->n_circuits);
     const VfCircuit& c = v->h_circ[0];
+    PLONK_REQUIRE(p->circuit.n_circuits == 1, PLONK_ERR_ARG, "a prover over a table of %u circuits is loaded with plonk_verifier_load_multi_prover", p->circuit.n_circuits);
     PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->circuit.ctx->device, v->ctx->device);
     PLONK_REQUIRE(p->circuit.log_n == c.log_n && p->circuit.n_public == c.n_public, PLONK_ERR_ARG, "the prover's circuit (2^%u rows, %zu public inputs) is not the verifier's (2^%u, %u)",
                   p->circuit.log_n, p->circuit.n_public, c.log_n, c.n_public);
@@ -743,6 +744,8 @@ int plonk_verifier_load_provers(plonk_verifier* v, size_t n_provers, plonk_prove
         PLONK_REQUIRE(p, PLONK_ERR_ARG, "prover %zu is null", i);
         PLONK_REQUIRE(circuit[i] < v->n_circuits, PLONK_ERR_ARG, "prover %zu: circuit %u of a table of %u", i, circuit[i], v->n_circuits);
         const VfCircuit& c = v->h_circ[circuit[i]];
+        PLONK_REQUIRE(p->circuit.n_circuits == 1, PLONK_ERR_ARG, "prover %zu is over a table of %u circuits: plonk_verifier_load_multi_prover loads it", i,
+                      p->circuit.n_circuits);
         PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "prover %zu lives on device %d, the verifier on %d", i, p->circuit.ctx->device, v->ctx->device);
         PLONK_REQUIRE(p->circuit.log_n == c.log_n && p->circuit.n_public == c.n_public, PLONK_ERR_ARG,
                       "prover %zu's circuit (2^%u rows, %zu public inputs) is not circuit %u of the table (2^%u, %u)", i, p->circuit.log_n, p->circuit.n_public,
@@ -774,6 +777,38 @@ int plonk_verifier_load_provers(plonk_verifier* v, size_t n_provers, plonk_prove
                                            v->ctx->stream));
         b += p->intake.resident_b;
     }
+    PLONK_TRY(verifier_meta_upload(v, batch, m));
+    return verifier_run(v, batch, seed, true);
+}
+
+// The resident batch of a prover over a table of circuits (plonk_prover_create_multi), packed on the device: proof b is labelled
+// circuit_map[the prover's label of b], and its public row is the prover's, [l_max] wide at b * l_max, of which the verifier reads its
+// circuit's own count.
+int plonk_verifier_load_multi_prover(plonk_verifier* v, plonk_prover* p, const uint32_t* circuit_map, const uint8_t seed[32]) {
+    PLONK_REQUIRE(v && p && circuit_map && seed, PLONK_ERR_ARG, "bad argument");
+    PLONK_REQUIRE(p->circuit.ctx->device == v->ctx->device, PLONK_ERR_ARG, "the prover lives on device %d, the verifier on %d", p->circuit.ctx->device, v->ctx->device);
+    for (unsigned k = 0; k < p->circuit.n_circuits; k++) {
+        PLONK_REQUIRE(circuit_map[k] < v->n_circuits, PLONK_ERR_ARG, "the prover's circuit %u: circuit %u of a table of %u", k, circuit_map[k], v->n_circuits);
+        const VfCircuit& c = v->h_circ[circuit_map[k]];
+        PLONK_REQUIRE(p->circuit.log_n == c.log_n && p->circuit.n_public_of[k] == c.n_public, PLONK_ERR_ARG,
+                      "the prover's circuit %u (2^%u rows, %zu public inputs) is not circuit %u of the table (2^%u, %u)", k, p->circuit.log_n,
+                      p->circuit.n_public_of[k], circuit_map[k], c.log_n, c.n_public);
+    }
+    const size_t batch = p->intake.resident_b, l_max = p->circuit.n_public;
+    PLONK_REQUIRE(batch, PLONK_ERR_STATE, "the prover has no resident batch");
+    PLONK_ENTER(v->ctx);
+    v->batch = 0;
+    VfMeta m;
+    PLONK_TRY(verifier_meta(v, batch, &m));
+    size_t n_pub = 0, n_inv = 0;
+    for (size_t b = 0; b < batch; b++) {
+        verifier_meta_set(v, m, b, circuit_map[p->labels.host[b]], &n_pub, &n_inv);
+        m.pub_off[b] = b * l_max;  // the prover's rows are not ragged
+    }
+    PLONK_TRY(verifier_ensure(v, batch, batch * l_max, n_inv));
+    PLONK_TRY(prover_pack_device(p, batch, 0, v->d_proofs, v->d_status, v->evs[0]));  // (its status bytes are overwritten, as above)
+    PLONK_CHECK_HIP(hipStreamWaitEvent(v->ctx->stream, v->evs[0], 0));
+    if (l_max) PLONK_CHECK_HIP(hipMemcpyAsync(v->d_pub, p->intake.pub, batch * l_max * sizeof(Fr), hipMemcpyDeviceToDevice, v->ctx->stream));
     PLONK_TRY(verifier_meta_upload(v, batch, m));
     return verifier_run(v, batch, seed, true);
 }

@@ -268,6 +268,24 @@ class MultiBatchVerifier(_Verifier):
         check(self.ctx.L.plonk_verifier_load_provers(self._h, n, handles, (ctypes.c_uint32 * n)(*ids), self._seed(seed)))
         self._loaded(B)
 
+    def load_prover(self, multi_prover, circuit_map=None, seed=None):
+        """The batch resident in a MultiBatchProver (after run()), mixed as it is, without a trip through the host.
+        `circuit_map[c]`: this table's id of the prover's circuit c; None = the two tables are in the same order."""
+        K = len(multi_prover.programs)
+        ids = self._ids(range(K) if circuit_map is None else circuit_map)
+        assert len(ids) == K, "circuit_map: %d entries, the prover's table holds %d circuits" % (len(ids), K)
+        self._batch = 0
+        check(self.ctx.L.plonk_verifier_load_multi_prover(self._h, multi_prover._h, (ctypes.c_uint32 * K)(*ids), self._seed(seed)))
+        self._loaded(multi_prover._resident)
+
+    def verify_prover(self, multi_prover, circuit_map=None, seed=None) -> bool:
+        self.load_prover(multi_prover, circuit_map, seed)
+        return self._verdict()
+
+    def verify_each_prover(self, multi_prover, circuit_map=None, seed=None, device=False):
+        self.load_prover(multi_prover, circuit_map, seed)
+        return self._verdicts(device)
+
     def verify(self, proofs, circuit_ids, publics, seed=None) -> bool:
         """BatchVerifier.verify for a mixed batch: one pairing check for all of it."""
         self.load(proofs, circuit_ids, publics, seed)
