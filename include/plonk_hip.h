@@ -183,6 +183,10 @@ int plonk_srs_lagrange(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, plonk_srs
 int plonk_srs_size(const plonk_srs* srs, size_t* out_n);
 int plonk_g1_msm(plonk_ctx* ctx, plonk_srs* srs, const void* d_scalars, size_t n, size_t batch,
                  size_t scalar_stride, uint8_t* h_out_xy_le, uint8_t* h_out_is_identity);
+/* How many MSMs of this context's LAST MSM call were recomputed by the method's recovery kernel (their deferred list overflowed, or,
+ * on a comb, a sum met equal or opposite operands): the counter of that call's recovery list, 0 for every call on well-formed inputs.
+ * Waits for the context's stream.  PLONK_ERR_ARG if the context has run no MSM or its last one failed (tests, diagnostics). */
+int plonk_msm_recovery_count(plonk_ctx* ctx, unsigned* out_count);
 /* Table MSM: for a reusable SRS (plonk_srs_load_ptau) a table per base is precomputed once into HBM, after which an MSM is
  * N * a mixed additions of looked-up points: no sorting, no buckets.  Two layouts, same results as the bucket method
  * (curve.py:38-111), bit for bit:

@@ -127,6 +127,12 @@ class Context:
         flags = (16 if windows else 0) | (32 if top else 0) | (64 if wide else 0) | {None: 0, "rows": 128, "lanes": 256}[walk]
         check(self.L.plonk_msm_lookup_configure(self.handle, mode | flags, bits, budget_bytes))
 
+    def msm_recovery_count(self):
+        """MSMs of the last MSM call that the comb's recovery kernel recomputed (0 on well-formed inputs)."""
+        n = ctypes.c_uint(0)
+        check(self.L.plonk_msm_recovery_count(self.handle, ctypes.byref(n)))
+        return n.value
+
     def profile(self, on):
         check(self.L.plonk_profile_enable(self.handle, 1 if on else 0))
 

@@ -737,6 +737,17 @@ int plonk_g1_msm(plonk_ctx* ctx, plonk_srs* srs, const void* d_scalars, size_t n
     return PLONK_OK;
 }
 
+int plonk_msm_recovery_count(plonk_ctx* ctx, unsigned* out_count) {
+    PLONK_REQUIRE(ctx && out_count, PLONK_ERR_ARG, "bad argument");
+    PLONK_ENTER(ctx);
+    PLONK_REQUIRE(ctx->msm_redo, PLONK_ERR_ARG, "this context has run no MSM (or its last one failed)");
+    uint32_t count = 0;
+    PLONK_CHECK_HIP(hipMemcpyAsync(&count, ctx->msm_redo, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+    PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    *out_count = count;
+    return PLONK_OK;
+}
+
 // ---- per-kernel profiling ------------------------------------------------------------------------
 int plonk_profile_enable(plonk_ctx* ctx, int on) {
     PLONK_REQUIRE(ctx, PLONK_ERR_ARG, "ctx is NULL");

@@ -35,6 +35,68 @@
 #define PLONK_DYN_SMEM(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
 #endif
 
+// PLONK_SHORT_KERNEL(): the first statement of every SHORT kernel on a batch's serial path — wave priority 3 for the wave's life.
+// The rule.  A batch is one stream, and a stream is one serial lane: while it sits in a kernel that does almost no work it feeds the
+// chip nothing.  Beside another stream's accumulation (msm_comb_rows_kernel: waves that live ~0.6 ms and keep 93 % of a SIMD's VALU
+// issue slots busy) such a kernel's waves are always the youngest on their SIMD, and issue is arbitrated by priority, then age: they
+// get the leftover slots and run three to five times their lone duration.  Priority outranks age, so these kernels take it:
+//   transcript_kernel; the comb MSM's digits, row-sum, column-sum, finalize and recovery kernels; every scan kernel of prover_scans.h;
+//   linearisation_weights / linearisation / gate_check / quotient_combine / pi_coeffs / pi_coset / pack_proofs / pack_status;
+//   the blinding correction kernels.
+// Together they issue under 5 % of a step's instructions, which is all the accumulation can lose to them.  The accumulation kernels
+// stay at priority 0: msm_comb_rows_kernel, msm_comb_kernel, the bucket and window accumulation kernels.
+// PLONK_WORK_KERNEL(): priority 1 for the other kernels that ARE a step's work but sit on a batch's serial path all the same — the
+// transforms (ntt_wavel_kernel, ntt_wavel_column_kernel, ntt_pass_radix2_kernel) and quotient_kernel, 14 % of the step's instructions.
+// Measured, not argued: with them at 0 the step was 201.95 ms, at 1 it was 199.97 (profiles/short_kernel_priority.json, variants).
+// The instruction is scalar and ignores EXEC: both macros are placed unconditionally, never under a branch.
+// Nothing in the host and emulator builds.  (A/B builds: make EXTRA="-DPLONK_SHORT_KERNEL_PRIORITY=0 -DPLONK_WORK_KERNEL_PRIORITY=0".)
+#ifndef PLONK_SHORT_KERNEL_PRIORITY
+#define PLONK_SHORT_KERNEL_PRIORITY 3
+#endif
+#ifndef PLONK_WORK_KERNEL_PRIORITY
+#define PLONK_WORK_KERNEL_PRIORITY 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PLONK_SHORT_KERNEL() __builtin_amdgcn_s_setprio(PLONK_SHORT_KERNEL_PRIORITY)
+#define PLONK_WORK_KERNEL() __builtin_amdgcn_s_setprio(PLONK_WORK_KERNEL_PRIORITY)
+#else
+#define PLONK_SHORT_KERNEL() ((void)0)
+#define PLONK_WORK_KERNEL() ((void)0)
+#endif
+
+// PLONK_BESIDE_ACC(lanes, bit): the launch bounds of a short kernel that has a SMALL FORM — compiled for five waves per SIMD, at most
+// 96 VGPRs, what is free on a SIMD beside four waves of msm_comb_rows_kernel (104 each of 512), so that its workgroups need not wait
+// for a whole accumulation workgroup to retire.  A kernel takes the small form where bit `bit` of PLONK_SMALL_FORMS is set: 1
+// msm_comb_finalize_kernel, 2 msm_comb_rowsum_kernel, 4 grand_product_kernel, 16 linearisation_weights_kernel.  (eval_kernel has no such
+// form: its 56 KB of LDS hold a SIMD to two waves, the compiler drops a request for five, and a direct cap — amdgpu_num_vgpr(96) —
+// gave 192 registers and 216 bytes of scratch.)  Each was
+// decided by measurement (profiles/short_kernel_priority.txt: registers, scratch and durations of both forms); the default is the
+// set that was kept: all four.  (A/B builds: make EXTRA=-DPLONK_SMALL_FORMS=0.)
+#ifndef PLONK_SMALL_FORMS
+#define PLONK_SMALL_FORMS 23
+#endif
+#define PLONK_BESIDE_ACC(lanes, bit) PLONK_BESIDE_ACC_##bit(lanes)
+#if (PLONK_SMALL_FORMS) & 1
+#define PLONK_BESIDE_ACC_1(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_1(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 2
+#define PLONK_BESIDE_ACC_2(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_2(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 4
+#define PLONK_BESIDE_ACC_4(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_4(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 16
+#define PLONK_BESIDE_ACC_16(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_16(lanes) __launch_bounds__(lanes)
+#endif
+
 // PLONK_CHAIN(acc): an empty statement that merely USES the running 64-bit column sum of a product-scanning
 // multiplication.  The second use makes every partial sum a leaf for LLVM's reassociation, which otherwise sums a
 // column's products from zero and adds the carry of the previous column last — one v_lshl_add_u64 per column, 16 per

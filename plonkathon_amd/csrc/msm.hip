@@ -220,6 +220,7 @@ int msm_run_device(plonk_ctx* ctx, plonk_srs* srs, const Fr* d_scalars, size_t n
     if (!inner) inner = M ? M : 1;
     PLONK_REQUIRE(n >= 1 && n <= srs->n_points, PLONK_ERR_ARG, "MSM size %zu exceeds the %zu loaded bases", n, srs->n_points);
     if (!M) return PLONK_OK;
+    ctx->msm_redo = nullptr;  // (scratch slot 1 may move below: the method's run sets it again once its kernels are enqueued)
     if (msm_table_prepare(ctx, srs)) return msm_layout(srs->shared->kind).run(ctx, srs, d_scalars, n, M, stride, d_out_xy, d_flags, inner, outer_stride);
     const unsigned c = ctx->msm_window_bits ? ctx->msm_window_bits : MSM_DEFAULT_WINDOW_BITS;
     return msm_run_bucket(ctx, srs, c, d_scalars, n, M, stride, d_out_xy, d_flags, inner, outer_stride);

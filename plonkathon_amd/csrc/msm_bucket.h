@@ -9,7 +9,7 @@
 __global__ void __launch_bounds__(MSM_BLOCK) msm_sort_kernel(const Fr* scalars, size_t n, size_t stride, size_t inner,
                                                              size_t outer_stride, unsigned c, unsigned W, MsmRecode rc,
                                                              uint32_t* entries, size_t entry_stride, uint32_t* starts,
-                                                             uint32_t* n_deferred) {
+                                                             uint32_t* n_deferred, uint32_t* redo) {
     PLONK_DYN_SMEM(smem);
     __shared__ uint32_t chunk_tot[MSM_BLOCK];
     const unsigned K = 1u << (c - 1);
@@ -53,6 +53,7 @@ __global__ void __launch_bounds__(MSM_BLOCK) msm_sort_kernel(const Fr* scalars, 
         st[K + 1] = chunk_tot[MSM_BLOCK - 1];
         st[0] = 0;
         n_deferred[m] = 0;
+        if (m == 0) redo[0] = 0;  // the recovery list's counter (msm_common.h)
     }
     __syncthreads();
     for (size_t i = tid; i < n; i += MSM_BLOCK) {
@@ -160,8 +161,8 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_accumulate_kerne
 __global__ void __launch_bounds__(256) msm_bucket_reduce_kernel(const uint32_t* starts, unsigned c, unsigned acc_lanes,
                                                                  const G1Xyzz* pieces, size_t piece_stride,
                                                                  const G1Affine* table, size_t table_n, const MsmDeferred* deferred,
-                                                                 size_t deferred_stride, const uint32_t* n_deferred,
-                                                                 Fq* out_xy, uint8_t* flags) {
+                                                                 size_t deferred_stride, const uint32_t* n_deferred, uint32_t* redo,
+                                                                 unsigned M, Fq* out_xy, uint8_t* flags) {
     PLONK_DYN_SMEM(smem);
     G1Xyzz* red = reinterpret_cast<G1Xyzz*>(smem);
     const unsigned K = 1u << (c - 1);
@@ -177,6 +178,7 @@ __global__ void __launch_bounds__(256) msm_bucket_reduce_kernel(const uint32_t* 
     // additions msm_accumulate_kernel left to the general formulas (normally 0); past the cap the MSM is redone by
     // msm_slow_kernel, which overwrites this kernel's output
     const uint32_t n_dfr = n_deferred[m] < MSM_DEFER_CAP ? n_deferred[m] : MSM_DEFER_CAP;
+    if (tid == 0 && n_deferred[m] > MSM_DEFER_CAP) msm_redo_append(redo, m, M);  // (the accumulation is over: the count is final; one lane per MSM)
     uint32_t s_hi = gst[b_hi + 1];
     for (unsigned k = b_hi; k > b_lo; k--) {
         const uint32_t s_lo = gst[k];
@@ -264,8 +266,9 @@ static int msm_run_bucket(plonk_ctx* ctx, plonk_srs* srs, unsigned c, const Fr* 
     MsmScratch s;
     const size_t ent_off = s.take(M * entry_stride * 4), st_off = s.take(M * (size_t)(K + 2) * 4), piece_off = s.take(M * piece_stride * sizeof(G1Xyzz));
     const size_t cnt_off = s.take(M * 4), dfr_off = s.take(M * MSM_DEFER_CAP * sizeof(MsmDeferred));  // bounded: an MSM that overflows is redone by msm_slow_kernel
+    const size_t redo_off = s.take(msm_redo_words(M) * sizeof(uint32_t));  // the recovery list: a part of its own, a counter and M indices
     PLONK_TRY(ctx_scratch(ctx, 1, s.total, (void**)&s.base));
-    uint32_t *entries = s.at<uint32_t>(ent_off), *starts = s.at<uint32_t>(st_off), *n_deferred = s.at<uint32_t>(cnt_off);
+    uint32_t *entries = s.at<uint32_t>(ent_off), *starts = s.at<uint32_t>(st_off), *n_deferred = s.at<uint32_t>(cnt_off), *redo = s.at<uint32_t>(redo_off);
     G1Xyzz* pieces = s.at<G1Xyzz>(piece_off);
     MsmDeferred* deferred = s.at<MsmDeferred>(dfr_off);
 
@@ -279,7 +282,7 @@ static int msm_run_bucket(plonk_ctx* ctx, plonk_srs* srs, unsigned c, const Fr* 
     }
     PLONK_TRY(prof_begin(ctx, "msm_sort", (double)M * 32.0 * (double)n));
     PLONK_LAUNCH(msm_sort_kernel, dim3((unsigned)M), dim3(MSM_BLOCK), sort_lds, ctx->stream, d_scalars, n, stride, inner, outer_stride, c, W, rc,
-                 entries, entry_stride, starts, n_deferred);
+                 entries, entry_stride, starts, n_deferred, redo);
     PLONK_TRY(prof_end(ctx));
     // algorithmic bytes of an MSM of size n: (64 + 32) * n + 64   
     PLONK_TRY(prof_begin(ctx, "msm_accumulate", (double)M * (96.0 * (double)n + 64.0)));
@@ -290,11 +293,12 @@ static int msm_run_bucket(plonk_ctx* ctx, plonk_srs* srs, unsigned c, const Fr* 
     PLONK_TRY(prof_begin(ctx, "msm_bucket_reduce", (double)M * (double)piece_stride * sizeof(G1Xyzz)));
     PLONK_LAUNCH(msm_bucket_reduce_kernel, dim3((unsigned)M), dim3(red_lanes), (size_t)red_lanes * sizeof(G1Xyzz), ctx->stream,
                  (const uint32_t*)starts, c, G * MSM_BLOCK, (const G1Xyzz*)pieces, piece_stride,
-                 (const G1Affine*)srs->table, srs->n_points, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred,
-                 d_out_xy, d_flags);
+                 (const G1Affine*)srs->table, srs->n_points, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred, redo,
+                 (unsigned)M, d_out_xy, d_flags);
     PLONK_TRY(prof_end(ctx));
-    PLONK_LAUNCH(msm_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, 1, (const G1Affine*)srs->table, srs->n_points, c, W,
-                 d_scalars, n, stride, inner, outer_stride, rc, (const uint32_t*)n_deferred, d_out_xy, d_flags);
+    PLONK_LAUNCH(msm_slow_kernel, dim3(msm_slow_grid(M)), dim3(256), 0, ctx->stream, 1, (const G1Affine*)srs->table, srs->n_points, c, W,
+                 d_scalars, n, stride, inner, outer_stride, rc, (const uint32_t*)redo, (unsigned)M, d_out_xy, d_flags);
     PLONK_CHECK_HIP(hipGetLastError());
+    ctx->msm_redo = redo;
     return PLONK_OK;
 }

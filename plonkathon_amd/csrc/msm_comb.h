@@ -40,7 +40,8 @@
 //   msm_comb_finalize_kernel    sum_j 2^j S_j by Horner over groups of LPM lanes per MSM, deferred additions, unique affine form; an
 //                               addition of OPPOSITE operands gives the identity here (an MSM whose result is the identity — all
 //                               scalars zero — cancels in these last additions, not before)
-//   msm_comb_slow_kernel        the recovery path of MSM_DEFER_CAP (general formulas throughout)
+//   msm_comb_slow_kernel        the recovery path of MSM_DEFER_CAP / MSM_COMB_REDO (general formulas throughout): 16 workgroups over the
+//                               list of MSMs that msm_comb_finalize_kernel found in need of it — empty in a prover's calls
 // Table build: msm_comb_scale_kernel gives P'_i; msm_table_kernel G_k = 2^(a k) P'_i; msm_comb_fill_kernel walks each run of 2^8 consecutive indices in
 // Gray-code order (one mixed addition of +-2 G_k per entry); g1_batch_to_affine_kernel converts a chunk of bases at a time;
 // msm_comb_top_base_kernel / msm_comb_top_fill_kernel: the joint tables, one block of 2^(h-1) entries per group behind the bases' blocks.
@@ -56,6 +57,7 @@
 // flag when a tree / Horner addition met equal or opposite operands.  Either way past the cap: msm_comb_slow_kernel redoes the MSM.
 #define MSM_COMB_REDO 0x80000000u
 PLONK_HD bool msm_comb_needs_redo(uint32_t v) { return (v & MSM_COMB_REDO) != 0 || v > MSM_DEFER_CAP; }
+// The MSMs to be redone go to the call's recovery list (msm_common.h): msm_comb_finalize_kernel appends, msm_comb_slow_kernel redoes.
 
 // A digit of this value stands for an item whose table entry is the identity — an identity base, the all-zero code of a group of
 // the top tables, a group past the last scalar — and every kernel that reads digits passes it over without a load.  No real item
@@ -275,7 +277,7 @@ __global__ void msm_comb_base_skip_kernel(const G1Affine* bases, size_t n, uint8
 // (nd = n + ceil(ceil(n / g) / A); a group past the last scalar gets the all-zero code: the identity entry of its block).
 // Items whose entry is the identity get MSM_COMB_SKIP: every column of an identity base (base_skip), and a group whose codes are all
 // zero — an identity base's code counts as zero, its share of every joint entry being the identity.  The kernel also zeroes
-// n_deferred[m]: it runs before the kernels that count.
+// n_deferred[m] and the counter of the recovery list (redo[0]): it runs before the kernels that count.
 // Layout: the digit of (row = m A + j, item i) is digits[row * rs + i * is].  Column-major (rs, is) = (nd, 1) is what msm_comb_kernel
 // reads; item-major (1, R), R = M A rows, is the row walk's (msm_comb_rows_kernel): there a lane's A digits lie next to each other
 // and, where A is a multiple of four (every row then starts on 16 bytes), leave as 16-byte stores.
@@ -286,7 +288,9 @@ __global__ void msm_comb_base_skip_kernel(const G1Affine* bases, size_t n, uint8
 template <unsigned H, bool TOP> __global__ void __launch_bounds__(256) msm_comb_digits_kernel(const Fr* scalars, size_t n, size_t stride, size_t inner,
                                                                                               size_t outer_stride, size_t m0, size_t m_end, unsigned tsh,
                                                                                               uint32_t* digits, size_t nd, size_t rs, size_t is,
-                                                                                              const uint8_t* base_skip, uint32_t* n_deferred) {
+                                                                                              const uint8_t* base_skip, uint32_t* n_deferred, uint32_t* redo) {
+    PLONK_SHORT_KERNEL();
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) redo[0] = 0;  // the recovery list's counter (its own part of the scratch: msm_redo_words)
     constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
     constexpr unsigned A = SH.a, L = A * H;
     static_assert(L <= 9 * 32 && H <= MSM_COMB_MAX_TEETH, "the recoded scalar is kept in nine words");
@@ -601,7 +605,8 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_comb_rows_kernel
 // 157 us per launch of 1 152 MSMs at G = 14 and a twelfth of the chip's issue slots, on a queue whose next kernel waits for it.  The layout is what msm_comb_finalize_kernel
 // reads with G = 1.
 #define MSM_ROWSUM_LANES 4
-__global__ void __launch_bounds__(64) msm_comb_rowsum_kernel(const G1Xyzz* partial, unsigned G, unsigned R, unsigned a, G1Xyzz* colsum, uint32_t* n_deferred) {
+__global__ void PLONK_BESIDE_ACC(64, 2) msm_comb_rowsum_kernel(const G1Xyzz* partial, unsigned G, unsigned R, unsigned a, G1Xyzz* colsum, uint32_t* n_deferred) {
+    PLONK_SHORT_KERNEL();
     const unsigned lane = threadIdx.x, row = blockIdx.x * (64 / MSM_ROWSUM_LANES) + lane / MSM_ROWSUM_LANES, l = lane % MSM_ROWSUM_LANES;
     G1XyzzL acc = g1l_identity();  // (a lane past the last row keeps the identity: every lane takes part in the exchanges)
     bool ok = true;
@@ -617,6 +622,7 @@ __global__ void __launch_bounds__(64) msm_comb_rowsum_kernel(const G1Xyzz* parti
 
 // colsum[m * a + j] = sum_g partial[(m * G + g) * a + j]: a wave per (MSM, column), lane g (G <= 64)
 __global__ void __launch_bounds__(64) msm_comb_colsum_kernel(const G1Xyzz* partial, unsigned G, unsigned a, G1Xyzz* colsum, uint32_t* n_deferred) {
+    PLONK_SHORT_KERNEL();
     const size_t m = blockIdx.x / a, j = blockIdx.x % a;
     const unsigned lane = threadIdx.x;
     G1XyzzL acc = g1l_identity();
@@ -636,17 +642,21 @@ __global__ void __launch_bounds__(64) msm_comb_colsum_kernel(const G1Xyzz* parti
 // takes the columns j = l (mod LPM) by Horner from the top (LPM doublings between two of them), doubles its share l more times,
 // and the LPM shares are summed by the cross-lane butterfly.  LPM = 1 is the plain Horner chain, one MSM per lane (least work:
 // a batch); larger groups shorten the chain of a - 1 serial doublings at the price of idle lanes (few MSMs: latency).
-template <unsigned LPM> __global__ void __launch_bounds__(64) msm_comb_finalize_kernel(const G1Xyzz* sums, size_t M, unsigned G, unsigned a,
+template <unsigned LPM> __global__ void PLONK_BESIDE_ACC(64, 1) msm_comb_finalize_kernel(const G1Xyzz* sums, size_t M, unsigned G, unsigned a,
                                                                                        const G1Affine* lookup, unsigned hb, size_t n,
                                                                                        const MsmDeferred* deferred, size_t deferred_stride,
-                                                                                       uint32_t* n_deferred, Fq* out_xy, uint8_t* flags, unsigned n_real,
-                                                                                       unsigned top_delta) {
+                                                                                       uint32_t* n_deferred, uint32_t* redo, Fq* out_xy, uint8_t* flags,
+                                                                                       unsigned n_real, unsigned top_delta) {
+    PLONK_SHORT_KERNEL();
     const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x, m = gid / LPM;
     const unsigned l = (unsigned)(gid % LPM), lane = threadIdx.x;
     G1XyzzL acc = g1l_identity();
     bool ok = true;  // false: an addition met equal or opposite operands — the MSM goes to msm_comb_slow_kernel
+    bool listed = false;  // lane 0 of the MSM: the kernels before this one left it to be redone
     if (m < M && l < a) {
-        const uint32_t nd = msm_comb_needs_redo(n_deferred[m]) ? 0u : n_deferred[m];  // (an MSM to be redone: its list may have holes, its sum is overwritten)
+        const uint32_t seen = n_deferred[m];
+        listed = l == 0 && msm_comb_needs_redo(seen);
+        const uint32_t nd = msm_comb_needs_redo(seen) ? 0u : seen;  // (an MSM to be redone: its list may have holes, its sum is overwritten)
         const unsigned jtop = l + ((a - 1 - l) / LPM) * LPM;
 #pragma unroll 1
         for (int j = (int)jtop; j >= 0; j -= (int)LPM) {
@@ -675,37 +685,49 @@ template <unsigned LPM> __global__ void __launch_bounds__(64) msm_comb_finalize_
     if constexpr (LPM >= 16) ok &= g1l_wave_reduce_step<8, true>(acc, lane);
     if constexpr (LPM >= 32) ok &= g1l_wave_reduce_step<16, true>(acc, lane);
     if constexpr (LPM >= 64) ok &= g1l_wave_reduce_step<32, true>(acc, lane);
-    if (m < M && !ok) atomicOr(n_deferred + m, MSM_COMB_REDO);
+    // The recovery list takes every MSM to be redone ONCE.  One flagged before this kernel (the accumulation's count past the cap, the
+    // tree's or the row sum's flag): its lane 0, and every atomicOr below then returns a value that already says "redo".  One whose
+    // first failed addition is here: the lane whose atomicOr returns a value that does not — the flag is never cleared, so one lane.
+    if (m < M && !ok && !msm_comb_needs_redo(atomicOr(n_deferred + m, MSM_COMB_REDO))) listed = true;
+    if (listed) msm_redo_append(redo, (uint32_t)m, (uint32_t)M);
     if (m < M && l == 0) msm_store_result(g1l_to_xyzz(acc), m, out_xy, flags);
 }
 
-// Recovery path (MSM_DEFER_CAP): MSM m recomputed from its digits with the general formulas; one workgroup per MSM, which exits
-// at once unless the MSM overflowed its deferred list.  Lane t: Horner over the columns of the scalars t, t + 256, ..
-// (rs, is): the digits' row and item strides (msm_comb_digits_kernel).
+// Recovery path (MSM_DEFER_CAP, MSM_COMB_REDO): every MSM of the recovery list recomputed from its digits with the general formulas.
+// A fixed grid of at most MSM_SLOW_GRID workgroups strides over the list, a workgroup per listed MSM at a time; with an empty
+// list — the normal case — every workgroup reads the counter and returns.  Lane t: Horner over the columns of the scalars t, t + 256, ..
+// (rs, is): the digits' row and item strides (msm_comb_digits_kernel).  M bounds the list (the counter cannot pass it: an MSM is
+// appended once).
 __global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits, size_t n, size_t rs,
-                                                            size_t is, const uint32_t* n_deferred, Fq* out_xy, uint8_t* flags, unsigned n_real,
+                                                            size_t is, const uint32_t* redo, unsigned M, Fq* out_xy, uint8_t* flags, unsigned n_real,
                                                             unsigned top_delta) {
+    PLONK_SHORT_KERNEL();
     __shared__ G1Xyzz red[256];
-    const unsigned m = blockIdx.x, tid = threadIdx.x;
-    if (!msm_comb_needs_redo(n_deferred[m])) return;
-    const uint32_t* dg = digits + (size_t)m * a * rs;
-    G1Xyzz acc = g1_xyzz_identity();
+    const unsigned tid = threadIdx.x, count = redo[0] < M ? redo[0] : M;
 #pragma unroll 1
-    for (int j = (int)a - 1; j >= 0; j--) {
-        g1_dbl(acc);
+    for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {  // (count is the same in every lane: the barriers below are reached by all)
+        const unsigned m = redo[1 + k];
+        if (m >= M) continue;  // (never: finalize appends indices below M; the same in every lane)
+        const uint32_t* dg = digits + (size_t)m * a * rs;
+        G1Xyzz acc = g1_xyzz_identity();
 #pragma unroll 1
-        for (size_t i = tid; i < n; i += 256) {
-            const uint32_t d = dg[(size_t)j * rs + i * is];
-            if (d == MSM_COMB_SKIP) continue;
-            const G1Affine* src = lookup + ((msm_comb_block_of(i, n_real, top_delta) << hb) + (d & 0x7fffffffu));
-            G1Affine pt;
-            pt.x = fp_load(&src->x);
-            pt.y = fp_load(&src->y);
-            if (d >> 31) pt.y = fp_neg(pt.y);
-            g1_madd<true>(acc, pt);
+        for (int j = (int)a - 1; j >= 0; j--) {
+            g1_dbl(acc);
+#pragma unroll 1
+            for (size_t i = tid; i < n; i += 256) {
+                const uint32_t d = dg[(size_t)j * rs + i * is];
+                if (d == MSM_COMB_SKIP) continue;
+                const G1Affine* src = lookup + ((msm_comb_block_of(i, n_real, top_delta) << hb) + (d & 0x7fffffffu));
+                G1Affine pt;
+                pt.x = fp_load(&src->x);
+                pt.y = fp_load(&src->y);
+                if (d >> 31) pt.y = fp_neg(pt.y);
+                g1_madd<true>(acc, pt);
+            }
         }
+        msm_fold_store(red, acc, tid, 256, m, out_xy, flags);
+        __syncthreads();  // red is written again for the workgroup's next MSM
     }
-    msm_fold_store(red, acc, tid, 256, m, out_xy, flags);
 }
 
 // Verification of a comb table found in the registry by its 64-bit key (msm_tables.h, lut_verified), against THIS SRS's bases:
@@ -896,7 +918,7 @@ static void msm_comb_verify(plonk_ctx* ctx, const plonk_srs* srs, const MsmLooku
 // comb with top tables, whose workgroups take whole groups of scalars and add the virtual scalars' digits (nd = n + their number)
 template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ctx, const Fr* d_scalars, size_t n, size_t stride, size_t inner,
                                                                    size_t outer_stride, size_t M, uint32_t* digits, size_t nd, bool item_major,
-                                                                   const uint8_t* base_skip, uint32_t* n_deferred) {
+                                                                   const uint8_t* base_skip, uint32_t* n_deferred, uint32_t* redo) {
     if constexpr (!TOP || msm_comb_top_ok(H)) {
         constexpr MsmCombShape SH = msm_comb_shape(H, TOP);
         constexpr unsigned G = TOP ? SH.top_g : 1;
@@ -907,15 +929,15 @@ template <unsigned H, bool TOP> static void msm_comb_launch_digits(plonk_ctx* ct
             const size_t gv = ((nd - n) * SH.a + PER / G - 1) / (PER / G);
             gx = gx > gv ? gx : gv;
         }
-        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, size_t, unsigned, uint32_t*, size_t, size_t, size_t, const uint8_t*, uint32_t*) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
+        void (*kern)(const Fr*, size_t, size_t, size_t, size_t, size_t, size_t, unsigned, uint32_t*, size_t, size_t, size_t, const uint8_t*, uint32_t*, uint32_t*) = msm_comb_digits_kernel<H, TOP>;  // (a template-id's comma would split the macro's arguments)
         for (size_t m0 = 0; m0 < M; m0 += (size_t)32768 << tsh) {  // (a grid's second dimension ends at 65 535)
             const size_t rows = M - m0 < ((size_t)32768 << tsh) ? M - m0 : (size_t)32768 << tsh;
             PLONK_LAUNCH(kern, dim3((unsigned)gx, (unsigned)((rows + (1u << tsh) - 1) >> tsh)), dim3(256), 0, ctx->stream, d_scalars, n, stride, inner,
-                         outer_stride, m0, M, tsh, digits, nd, rs, is, base_skip, n_deferred);
+                         outer_stride, m0, M, tsh, digits, nd, rs, is, base_skip, n_deferred, redo);
         }
     }
 }
-typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, bool, const uint8_t*, uint32_t*);
+typedef void (*msm_comb_digits_fn)(plonk_ctx*, const Fr*, size_t, size_t, size_t, size_t, size_t, uint32_t*, size_t, bool, const uint8_t*, uint32_t*, uint32_t*);
 template <bool TOP, unsigned... H> static msm_comb_digits_fn msm_comb_digits_for(unsigned h, std::integer_sequence<unsigned, H...>) {
     msm_comb_digits_fn fn = nullptr;
     ((h == H + 2 && (!TOP || msm_comb_top_ok(H + 2)) ? (void)(fn = &msm_comb_launch_digits<H + 2, TOP>) : (void)0), ...);
@@ -933,17 +955,18 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     const unsigned top_delta = (unsigned)(srs->n_points - n_real);  // block of virtual scalar n_real + v = n_points + v (+ the digit's offset)
     PLONK_REQUIRE((uint64_t)n * a < ((uint64_t)1 << 32), PLONK_ERR_ARG, "MSM size %zu too large for the lookup path", n_real);
     PLONK_REQUIRE(msm_comb_top_reach_ok(n_real, sh), PLONK_ERR_ARG, "MSM size %zu too large for the top tables of %u teeth", n_real, h);
+    PLONK_REQUIRE(M < ((size_t)1 << 31), PLONK_ERR_ARG, "%zu MSMs are too many for one call", M);  // (an MSM's index is a 32-bit word of the recovery list)
     // Which accumulation kernel.  The row walk (msm_comb_rows_kernel) launches W = ceil(R / 256) workgroups of rows times G chunks of
-    // scalars, THREE rounds of the chip's workgroup slots: G = 3 slots / W, lowered until a chunk holds 32 scalars (a chunk's flush
-    // and its addition in the row sum cost about 1.3 additions: under 4 %).  One round — every slot filled exactly once — is the
-    // least overhead and the slowest step: the launch then holds the whole chip for its length and lets go of it at once, so the
-    // other streams' kernels cannot fill in beside it (20 streams: 208.2 ms per step at one round, 204.6 at 1.5, 202.2 - 203.1 at
-    // two, 201.0 at three, against the column-lane kernel's 205.0 - 205.6; docs/HISTORY.md).  It is taken when W G fills half the
+    // scalars, TWO rounds of the chip's workgroup slots: G = 2 slots / W, lowered until a chunk holds 32 scalars (a chunk's flush
+    // and its addition in the row sum cost about 1.3 additions).  One round — every slot filled exactly once — is the least overhead
+    // and the slowest step: the launch holds the whole chip for its length, and the other streams' kernels cannot fill in beside it;
+    // more rounds buy less than their flushes cost since the short kernels take issue slots by priority (measured one to three
+    // rounds, twice: docs/HISTORY.md).  It is taken when W G fills half the
     // slots; fewer MSMs — the latency paths — keep msm_comb_kernel, whose workgroups split ONE MSM.  ctx->msm_groups has no say here: it means workgroups
     // per MSM, for msm_comb_kernel alone.  Test flags (plonk_msm_lookup_configure mode | 128, | 256) force either form; with the row
     // walk forced a non-zero msm_groups is the chunk count, which makes several chunks reachable at toy sizes.
     const size_t R = M * a, W = (R + MSM_BLOCK - 1) / MSM_BLOCK, slots = 4 * (size_t)device_cus(ctx->device);
-    size_t Gr = 3 * slots / W ? 3 * slots / W : 1;
+    size_t Gr = 2 * slots / W ? 2 * slots / W : 1;
     if (Gr > n / 32) Gr = n / 32 ? n / 32 : 1;
     bool rows = ctx->msm_comb_walk == 1 || (ctx->msm_comb_walk == 0 && W * Gr >= slots / 2);
     if (ctx->msm_comb_walk == 1 && ctx->msm_groups) Gr = ctx->msm_groups < n ? ctx->msm_groups : n;
@@ -957,9 +980,10 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     MsmScratch s;
     const size_t part_off = s.take(M * G * a * sizeof(G1Xyzz)), col_off = s.take(rows || G >= 4 ? M * a * sizeof(G1Xyzz) : 0), cnt_off = s.take(M * 4);
     const size_t dfr_off = s.take(M * MSM_DEFER_CAP * sizeof(MsmDeferred)), dig_off = s.take(M * a * n * 4);
+    const size_t redo_off = s.take(msm_redo_words(M) * sizeof(uint32_t));  // the recovery list: a part of its own, a counter and M indices
     PLONK_TRY(ctx_scratch(ctx, 1, s.total, (void**)&s.base));
     G1Xyzz *partial = s.at<G1Xyzz>(part_off), *colsum = s.at<G1Xyzz>(col_off);
-    uint32_t *n_deferred = s.at<uint32_t>(cnt_off), *digits = s.at<uint32_t>(dig_off);
+    uint32_t *n_deferred = s.at<uint32_t>(cnt_off), *digits = s.at<uint32_t>(dig_off), *redo = s.at<uint32_t>(redo_off);
     MsmDeferred* deferred = s.at<MsmDeferred>(dfr_off);
     const auto teeth = std::make_integer_sequence<unsigned, MSM_COMB_MAX_TEETH - 1>();
     const msm_comb_digits_fn digits_fn = top ? msm_comb_digits_for<true>(h, teeth) : msm_comb_digits_for<false>(h, teeth);
@@ -967,7 +991,7 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     PLONK_TRY(prof_begin(ctx, "msm_digits", (double)M * (double)n * (32.0 + 4.0 * a)));
     // digits: column-major digits[row][i] for msm_comb_kernel, item-major digits[i][row] for the row walk
     const size_t dig_rs = rows ? 1 : n, dig_is = rows ? R : 1;
-    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n, rows, srs->shared->base_skip, n_deferred);  // (also zeroes n_deferred)
+    digits_fn(ctx, d_scalars, n_real, stride, inner, outer_stride, M, digits, n, rows, srs->shared->base_skip, n_deferred, redo);  // (also zeroes n_deferred and the recovery list's counter)
     PLONK_TRY(prof_end(ctx));
     const size_t lds = (size_t)(MSM_BLOCK + a) * sizeof(G1Xyzz);
     PLONK_TRY(prof_begin(ctx, "msm_comb", (double)M * (96.0 * (double)n_real + 64.0)));  // (the accumulation, whichever kernel runs it)
@@ -1001,13 +1025,15 @@ static int msm_run_comb(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_scalar
     // one lane per MSM would be the least work and the longest chain (12 + 12).
 #define PLONK_COMB_FINALIZE(L)                                                                                                                      \
     PLONK_LAUNCH(msm_comb_finalize_kernel<L>, dim3((unsigned)((M * L + 63) / 64)), dim3(64), 0, ctx->stream, sums, M, Gf, a, table, hb, n,            \
-                 (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, n_deferred, d_out_xy, d_flags, (unsigned)n_real, top_delta)
+                 (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, n_deferred, redo, d_out_xy, d_flags, (unsigned)n_real, top_delta)
     if (M >= 64) PLONK_COMB_FINALIZE(4);
     else PLONK_COMB_FINALIZE(16);
 #undef PLONK_COMB_FINALIZE
-    PLONK_LAUNCH(msm_comb_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, n, dig_rs, dig_is,
-                 (const uint32_t*)n_deferred, d_out_xy, d_flags, (unsigned)n_real, top_delta);
+    // the recovery kernel: a fixed small grid over the list finalize left (empty in every call of a prover: 16 workgroups read one word)
+    PLONK_LAUNCH(msm_comb_slow_kernel, dim3(msm_slow_grid(M)), dim3(256), 0, ctx->stream, table, hb, a, (const uint32_t*)digits, n, dig_rs, dig_is,
+                 (const uint32_t*)redo, (unsigned)M, d_out_xy, d_flags, (unsigned)n_real, top_delta);
     PLONK_CHECK_HIP(hipGetLastError());
+    ctx->msm_redo = redo;  // (every kernel that writes the list is enqueued: plonk_msm_recovery_count)
     return PLONK_OK;
 }
 

@@ -87,43 +87,67 @@ PLONK_DEV void msm_fold_store(G1Xyzz* red, const G1Xyzz& share, unsigned tid, un
     if (tid == 0) msm_store_result(total, m, out_xy, flags);
 }
 
-// Recovery path (see MSM_DEFER_CAP): MSM m is recomputed with the general addition formulas, which handle every
-// exceptional case (identity, P == Q, P == -Q), and its output overwritten.  One workgroup per MSM; it exits at
-// once unless the MSM overflowed its deferred list, so the launch costs a few microseconds on the normal path.
+// The RECOVERY LIST of a call of M MSMs, a part of the call's scratch of its own (msm_run_comb / msm_run_windows / msm_run_bucket):
+// redo[0] counts the MSMs that need the method's recovery kernel and redo[1 .. 1 + count) holds their indices, each once, in no
+// particular order (count <= M: the part has 1 + M words).  The counter is zeroed where n_deferred is (the comb's digit kernel, the
+// bucket method's sort kernel, the window tables' memset); the method's LAST kernel before the recovery kernel — the one place
+// that sees an MSM's final count — appends; the recovery kernel strides over the list on a small fixed grid.  A call that needs no
+// recovery — every call of a prover — pays a launch of MSM_SLOW_GRID workgroups that read one word, where one workgroup per MSM read
+// one flag each.
+#define MSM_SLOW_GRID 16
+PLONK_HD size_t msm_redo_words(size_t M) { return M + 1; }
+// (the slot is the atomic's return: appends from any lanes of any workgroups land in distinct words; the caller sees to it that an MSM
+// is appended once, so the slot is below M: the comparison only keeps a counter that was never zeroed from writing outside the part)
+PLONK_DEV void msm_redo_append(uint32_t* redo, uint32_t m, uint32_t M) {
+    const uint32_t slot = atomicAdd(redo, 1u);
+    if (slot < M) redo[1 + slot] = m;
+}
+static unsigned msm_slow_grid(size_t M) { return M < MSM_SLOW_GRID ? (unsigned)M : MSM_SLOW_GRID; }
+
+// Recovery path (see MSM_DEFER_CAP): every MSM of the recovery list is recomputed with the general addition formulas, which handle
+// every exceptional case (identity, P == Q, P == -Q), and its output overwritten.  At most MSM_SLOW_GRID workgroups stride over
+// the list, a workgroup per listed MSM at a time; with an empty list — the normal case — every workgroup reads the counter and
+// returns.  M bounds the list.
 // kind 0: window tables (entry |d| of item (i, w));  kind 1: the bucket method's T[w][i] (|d| * T by double-and-add).
 __global__ void __launch_bounds__(256) msm_slow_kernel(int kind, const G1Affine* tab, size_t table_n, unsigned c, unsigned W,
                                                        const Fr* scalars, size_t n, size_t stride, size_t inner,
-                                                       size_t outer_stride, MsmRecode rc, const uint32_t* n_deferred,
+                                                       size_t outer_stride, MsmRecode rc, const uint32_t* redo, unsigned M,
                                                        Fq* out_xy, uint8_t* flags) {
+    PLONK_SHORT_KERNEL();
     __shared__ G1Xyzz red[256];
-    const unsigned m = blockIdx.x, tid = threadIdx.x;
-    if (n_deferred[m] <= MSM_DEFER_CAP) return;
-    const Fr* sc = msm_scalar_row(scalars, m, stride, inner, outer_stride);
-    G1Xyzz acc = g1_xyzz_identity();
-    for (size_t i = tid; i < n; i += 256) {
-        uint32_t limb[10];
-        msm_recode(sc, i, rc, limb);
-        msm_for_each_digit(limb, c, W, [&](unsigned w, int d) {
-            if (!d) return;
-            const uint32_t ad = d < 0 ? (uint32_t)-d : (uint32_t)d;
-            const G1Affine* src = kind == 0 ? tab + ((((size_t)w * table_n + i) << (c - 1)) + (ad - 1)) : tab + (size_t)w * table_n + i;
-            G1Affine pt;
-            pt.x = fp_load(&src->x);
-            pt.y = fp_load(&src->y);
-            if (d < 0) pt.y = fp_neg(pt.y);
-            if (kind == 0) {
-                g1_madd<true>(acc, pt);
-            } else {
-                G1Xyzz t = g1_xyzz_identity();
-                for (int bit = (int)c - 1; bit >= 0; bit--) {
-                    g1_dbl(t);
-                    if ((ad >> bit) & 1) g1_madd<true>(t, pt);
+    const unsigned tid = threadIdx.x, count = redo[0] < M ? redo[0] : M;
+#pragma unroll 1
+    for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {  // (count is the same in every lane: the barriers below are reached by all)
+        const unsigned m = redo[1 + k];
+        if (m >= M) continue;  // (never: only indices below M are appended; the same in every lane)
+        const Fr* sc = msm_scalar_row(scalars, m, stride, inner, outer_stride);
+        G1Xyzz acc = g1_xyzz_identity();
+        for (size_t i = tid; i < n; i += 256) {
+            uint32_t limb[10];
+            msm_recode(sc, i, rc, limb);
+            msm_for_each_digit(limb, c, W, [&](unsigned w, int d) {
+                if (!d) return;
+                const uint32_t ad = d < 0 ? (uint32_t)-d : (uint32_t)d;
+                const G1Affine* src = kind == 0 ? tab + ((((size_t)w * table_n + i) << (c - 1)) + (ad - 1)) : tab + (size_t)w * table_n + i;
+                G1Affine pt;
+                pt.x = fp_load(&src->x);
+                pt.y = fp_load(&src->y);
+                if (d < 0) pt.y = fp_neg(pt.y);
+                if (kind == 0) {
+                    g1_madd<true>(acc, pt);
+                } else {
+                    G1Xyzz t = g1_xyzz_identity();
+                    for (int bit = (int)c - 1; bit >= 0; bit--) {
+                        g1_dbl(t);
+                        if ((ad >> bit) & 1) g1_madd<true>(t, pt);
+                    }
+                    g1_add(acc, t);
                 }
-                g1_add(acc, t);
-            }
-        });
+            });
+        }
+        msm_fold_store(red, acc, tid, 256, m, out_xy, flags);
+        __syncthreads();  // red is written again for the workgroup's next MSM
     }
-    msm_fold_store(red, acc, tid, 256, m, out_xy, flags);
 }
 
 // ---- host side ---------------------------------------------------------------------------------

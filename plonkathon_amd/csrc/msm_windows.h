@@ -117,8 +117,10 @@ __global__ void __launch_bounds__(MSM_BLOCK, MSM_ACC_WAVES) msm_lookup_kernel(
 
 // acc += the deferred additions of MSM m
 PLONK_DEV void msm_windows_add_deferred(G1Xyzz& acc, size_t m, const G1Affine* lookup, size_t table_n, unsigned c, unsigned W,
-                                        const MsmDeferred* deferred, size_t deferred_stride, const uint32_t* n_deferred) {
+                                        const MsmDeferred* deferred, size_t deferred_stride, const uint32_t* n_deferred, uint32_t* redo,
+                                        size_t M) {
     const uint32_t nd = n_deferred[m] < MSM_DEFER_CAP ? n_deferred[m] : MSM_DEFER_CAP;  // past the cap: msm_slow_kernel
+    if (n_deferred[m] > MSM_DEFER_CAP) msm_redo_append(redo, (uint32_t)m, (uint32_t)M);  // (called by one lane per MSM, after the accumulation)
     for (uint32_t k = 0; k < nd; k++) {
         const MsmDeferred e = deferred[m * deferred_stride + k];
         const uint32_t i = e.bucket / W, w = e.bucket - i * W;  // `bucket` carries the item index here
@@ -136,12 +138,12 @@ PLONK_DEV void msm_windows_add_deferred(G1Xyzz& acc, size_t m, const G1Affine* l
 // out_xy[m] = canonical affine of sum_g partial[m][g] + the deferred additions; flags[m] = 1 for the identity
 __global__ void __launch_bounds__(64) msm_lookup_finalize_kernel(const G1Xyzz* partial, size_t M, unsigned G, const G1Affine* lookup,
                                                                  size_t table_n, unsigned c, unsigned W, const MsmDeferred* deferred,
-                                                                 size_t deferred_stride, const uint32_t* n_deferred, Fq* out_xy,
-                                                                 uint8_t* flags) {
+                                                                 size_t deferred_stride, const uint32_t* n_deferred, uint32_t* redo,
+                                                                 Fq* out_xy, uint8_t* flags) {
     for (size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (size_t)gridDim.x * blockDim.x) {
         G1Xyzz acc = partial[m * G];
         for (unsigned g = 1; g < G; g++) g1_add(acc, partial[m * G + g]);
-        msm_windows_add_deferred(acc, m, lookup, table_n, c, W, deferred, deferred_stride, n_deferred);
+        msm_windows_add_deferred(acc, m, lookup, table_n, c, W, deferred, deferred_stride, n_deferred, redo, M);
         msm_store_result(acc, m, out_xy, flags);
     }
 }
@@ -151,8 +153,8 @@ __global__ void __launch_bounds__(64) msm_lookup_finalize_kernel(const G1Xyzz* p
 // serial form made a lone 2^11 commitment 0.75 ms, most of the reference-shaped Prover's latency); lane 0 finishes.
 __global__ void __launch_bounds__(64) msm_lookup_finalize_wave_kernel(const G1Xyzz* partial, size_t M, unsigned G, const G1Affine* lookup,
                                                                       size_t table_n, unsigned c, unsigned W, const MsmDeferred* deferred,
-                                                                      size_t deferred_stride, const uint32_t* n_deferred, Fq* out_xy,
-                                                                      uint8_t* flags) {
+                                                                      size_t deferred_stride, const uint32_t* n_deferred, uint32_t* redo,
+                                                                      Fq* out_xy, uint8_t* flags) {
     const size_t m = blockIdx.x;
     const unsigned lane = threadIdx.x;
     G1Xyzz acc = g1_xyzz_identity();
@@ -162,7 +164,7 @@ __global__ void __launch_bounds__(64) msm_lookup_finalize_wave_kernel(const G1Xy
     }
     g1_wave_reduce(acc, lane);
     if (lane) return;
-    msm_windows_add_deferred(acc, m, lookup, table_n, c, W, deferred, deferred_stride, n_deferred);
+    msm_windows_add_deferred(acc, m, lookup, table_n, c, W, deferred, deferred_stride, n_deferred, redo, M);
     msm_store_result(acc, m, out_xy, flags);
 }
 
@@ -262,9 +264,10 @@ static int msm_run_windows(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_sca
     const unsigned G = msm_groups_per_msm(ctx, M, 64, 3072 / (MSM_BLOCK / 64), 0.027, items, 2);
     MsmScratch s;
     const size_t part_off = s.take(M * G * sizeof(G1Xyzz)), cnt_off = s.take(M * 4), dfr_off = s.take(M * MSM_DEFER_CAP * sizeof(MsmDeferred));
+    const size_t redo_off = s.take(msm_redo_words(M) * sizeof(uint32_t));  // the recovery list: a part of its own, a counter and M indices
     PLONK_TRY(ctx_scratch(ctx, 1, s.total, (void**)&s.base));
     G1Xyzz* partial = s.at<G1Xyzz>(part_off);
-    uint32_t* n_deferred = s.at<uint32_t>(cnt_off);
+    uint32_t *n_deferred = s.at<uint32_t>(cnt_off), *redo = s.at<uint32_t>(redo_off);
     MsmDeferred* deferred = s.at<MsmDeferred>(dfr_off);
     MsmRecode rc;
     msm_recode_constant(c, W, &rc);
@@ -272,6 +275,7 @@ static int msm_run_windows(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_sca
     // contiguous 1 - 2 GB of the table at a time, which the translation caches hold (see msm_lookup_kernel)
     const unsigned strided = n >= (size_t)G * MSM_BLOCK ? 1u : 0u;
     PLONK_CHECK_HIP(hipMemsetAsync(n_deferred, 0, M * 4, ctx->stream));
+    PLONK_CHECK_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), ctx->stream));  // the recovery list's counter
     PLONK_TRY(prof_begin(ctx, "msm_lookup", (double)M * (96.0 * (double)n + 64.0)));
     PLONK_LAUNCH(msm_lookup_kernel, dim3((unsigned)(M * G)), dim3(MSM_BLOCK), (size_t)MSM_BLOCK * sizeof(G1Xyzz), ctx->stream, table,
                  srs->n_points, c, W, d_scalars, n, stride, inner, outer_stride, rc, G, partial, deferred, (size_t)MSM_DEFER_CAP, n_deferred,
@@ -279,13 +283,14 @@ static int msm_run_windows(plonk_ctx* ctx, const plonk_srs* srs, const Fr* d_sca
     PLONK_TRY(prof_end(ctx));
     if (G >= 8)  // few MSMs in many pieces: a wave per MSM sums the pieces in parallel
         PLONK_LAUNCH(msm_lookup_finalize_wave_kernel, dim3((unsigned)M), dim3(64), 0, ctx->stream, (const G1Xyzz*)partial, M, G, table,
-                     srs->n_points, c, W, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred, d_out_xy, d_flags);
+                     srs->n_points, c, W, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred, redo, d_out_xy, d_flags);
     else
         PLONK_LAUNCH(msm_lookup_finalize_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, ctx->stream, (const G1Xyzz*)partial, M, G, table,
-                     srs->n_points, c, W, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred, d_out_xy, d_flags);
-    PLONK_LAUNCH(msm_slow_kernel, dim3((unsigned)M), dim3(256), 0, ctx->stream, 0, table, srs->n_points, c, W, d_scalars, n, stride, inner,
-                 outer_stride, rc, (const uint32_t*)n_deferred, d_out_xy, d_flags);
+                     srs->n_points, c, W, (const MsmDeferred*)deferred, (size_t)MSM_DEFER_CAP, (const uint32_t*)n_deferred, redo, d_out_xy, d_flags);
+    PLONK_LAUNCH(msm_slow_kernel, dim3(msm_slow_grid(M)), dim3(256), 0, ctx->stream, 0, table, srs->n_points, c, W, d_scalars, n, stride, inner,
+                 outer_stride, rc, (const uint32_t*)redo, (unsigned)M, d_out_xy, d_flags);
     PLONK_CHECK_HIP(hipGetLastError());
+    ctx->msm_redo = redo;
     return PLONK_OK;
 }
 

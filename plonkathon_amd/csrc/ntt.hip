@@ -63,6 +63,7 @@ PLONK_DEV void lds_st(u32x4* lo, u32x4* hi, unsigned i, const Fr& a) {
 PLONK_DEV unsigned bitrev(unsigned x, unsigned bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
 
 __global__ void __launch_bounds__(1024) ntt_pass_radix2_kernel(NttPass p) {
+    PLONK_WORK_KERNEL();
     PLONK_DYN_SMEM(smem);
     const unsigned R = 1u << p.log_r, C = 1u << p.log_c;
     const unsigned T = R * C;

@@ -591,6 +591,7 @@ PLONK_DEV void wavel_transform(const NttWaveT<P>& p, unsigned char* smem) {
 
 template <class P, unsigned LOG_E, unsigned NLDS>
 __global__ void __launch_bounds__(1u << wavel_log_t(NLDS), (WavelCfg<LOG_E, NLDS>::WAVES)) ntt_wavel_kernel(NttWaveT<P> p) {
+    PLONK_WORK_KERNEL();
     PLONK_DYN_SMEM(smem);
     wavel_transform<P, LOG_E, NLDS>(p, smem);
 }
@@ -599,6 +600,7 @@ __global__ void __launch_bounds__(1u << wavel_log_t(NLDS), (WavelCfg<LOG_E, NLDS
 // 8 %, profiles/r03_q_ntt_e8_column_table_ab.jsonl)
 template <class P, unsigned LOG_E, unsigned NLDS>
 __global__ void __launch_bounds__(1u << wavel_log_t(NLDS), (WavelCfg<LOG_E, NLDS>::WAVES)) ntt_wavel_column_kernel(NttWaveT<P> p) {
+    PLONK_WORK_KERNEL();
     PLONK_DYN_SMEM(smem);
     wavel_transform<P, LOG_E, NLDS, true>(p, smem);
 }

@@ -169,6 +169,10 @@ struct plonk_ctx {
     bool msm_lookup_top = false;     // with explicit msm_lookup_bits: the comb WITH top tables (plonk_msm_lookup_configure mode | 32)
     bool msm_comb_wide = false;      // test flag (plonk_msm_lookup_configure mode | 64): the comb kernel with the 64-bit entry index whatever the table's size
     unsigned msm_comb_walk = 0;      // test flags (plonk_msm_lookup_configure mode | 128, | 256): 1 the comb's row walk, 2 its column-lane kernel, whatever the rule says (0)
+    // device: the recovery list of this context's last MSM call (msm_common.h; its first word counts the MSMs redone), read by
+    // plonk_msm_recovery_count.  It points INTO scratch slot 1, which ctx_scratch may free and move: valid only because every user of slot 1
+    // goes through msm_run_device, which clears it before the method's run takes the slot and sets it after enqueueing its kernels.
+    uint32_t* msm_redo = nullptr;
     unsigned msm_lookup_kind = MSM_TABLE_COMB;  // layout of the tables this context builds (plonk_msm_lookup_configure: mode | 16 = window tables)
     size_t msm_lookup_budget = 0;    // bytes; 0 = default (PLONK_MSM_TABLE_GB if set, else min(device memory / 16, free memory / 4): msm_tables.h)
     bool ntt_attr_set = false, msm_attr_set = false;  // hipFuncSetAttribute is per device: tracked per context

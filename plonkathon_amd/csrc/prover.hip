@@ -36,6 +36,7 @@
 //   coefficient j of L_i is  w^(-ij) / n            (an inverse DFT of a unit vector)
 //   L_i(x) = (w^i / n) (x^n - 1) / (x - w^i)        (li_big holds it on the coset points: [3][n] coset-major)
 __global__ void pi_coeffs_kernel(const Fr* pub, size_t l, const Fr* roots_inv, size_t n, size_t B, Fr n_inv, Fr* pic) {
+    PLONK_SHORT_KERNEL();
     const size_t total = B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n, j = gI - b * n;
@@ -45,6 +46,7 @@ __global__ void pi_coeffs_kernel(const Fr* pub, size_t l, const Fr* roots_inv, s
     }
 }
 __global__ void pi_coset_kernel(const Fr* pub, size_t l, const Fr* li_big, size_t n4, size_t B, Fr* pi_big) {
+    PLONK_SHORT_KERNEL();
     const size_t total = B * n4;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n4, k = gI - b * n4;
@@ -70,6 +72,7 @@ __global__ void li_coset_kernel(const Fr* xs, const Fr* roots, size_t n4, size_t
 // sh.msg; an identity commitment (flag set) is absorbed as zeros and reported through `error`.
 __global__ void __launch_bounds__(2 * TC_LANES) transcript_kernel(int round, ProofState* st, size_t B, const Fq* commit_xy,
                                                                   const uint8_t* flags, ChallengeConsts cc) {
+    PLONK_SHORT_KERNEL();
     __shared__ TcShared shared[2];
     const unsigned grp = threadIdx.x / TC_LANES, lane = threadIdx.x % TC_LANES;
     TcShared& sh = shared[grp];
@@ -128,6 +131,7 @@ struct QuotientIn { const Fr* wit[5]; const Fr* fixed[FX_COUNT]; const Fr* l0; c
 // each line ("n" = normalised: limbs 0..7 in [0, 2^29)); the emulator build asserts them on every operand.
 __global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, const ProofState* st, RoundChallenges direct, unsigned n4, Fr* quot,
                                                        unsigned coset_log, unsigned out_stride) {
+    PLONK_WORK_KERNEL();
     typedef FpL<FrParams> L;
     // blockIdx.y = proof, blockIdx.x * blockDim.x + threadIdx.x = point (32-bit indices, no divisions)
     const unsigned b = blockIdx.y;
@@ -182,6 +186,7 @@ __global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, 
 //   =>  s_1 = u_0/2 - u_2/2,   p = t_i + s_2 = u_0/2 + u_2/2,   m = t_i - s_2 = u_1 - i s_1,   t_i = (p + m)/2,  s_2 = (p - m)/2.
 // in place: slice q of quot[b] <- T_q.  Three multiplications per i (by i, 1/g^n, 1/(2 g^2n)) and a halving.
 __global__ void quotient_combine_kernel(Fr* quot, size_t n, size_t stride, size_t B, Fr ci, Fr g1_inv, Fr g2_inv_half, Fr half) {
+    PLONK_SHORT_KERNEL();
     const size_t total = B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n, i = gI - b * n;
@@ -201,6 +206,7 @@ __global__ void quotient_combine_kernel(Fr* quot, size_t n, size_t stride, size_
 // quotient interpolated from 3n points no longer has.  fixed_lag: [K][8][n], proof b's circuit is cid[b] (cid == null: circuit 0).
 __global__ void gate_check_kernel(const Fr* abc, const Fr* pub, size_t l, const Fr* pi_or_null, const Fr* fixed_lag, const uint32_t* cid, size_t n, size_t B,
                                   uint32_t* bad) {
+    PLONK_SHORT_KERNEL();
     const size_t total = B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n, i = gI - b * n;
@@ -257,7 +263,8 @@ PLONK_DEV LinWeights linearisation_weights(const ProofState& s, unsigned log_n, 
 }
 
 // one lane per proof: the 15 weights (one field inversion each) are computed once, not once per tile
-__global__ void __launch_bounds__(64) linearisation_weights_kernel(const ProofState* st, unsigned log_n, Fr n_inv, size_t B, LinWeights* out) {
+__global__ void PLONK_BESIDE_ACC(64, 16) linearisation_weights_kernel(const ProofState* st, unsigned log_n, Fr n_inv, size_t B, LinWeights* out) {
+    PLONK_SHORT_KERNEL();
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) out[b] = linearisation_weights(st[b], log_n, n_inv);
 }
@@ -268,6 +275,7 @@ __global__ void __launch_bounds__(64) linearisation_weights_kernel(const ProofSt
 __global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr* tcoef,
                                                               const LinWeights* weights, unsigned log_n, size_t B,
                                                               Fr* out) {
+    PLONK_SHORT_KERNEL();
     typedef FpL<FrParams> L;
     __shared__ int32_t WL[16][12];  // the weights as limbs (9 of 12 words used); [15] = R mod m, the Montgomery form of 1
     const size_t n = (size_t)1 << log_n;
@@ -315,6 +323,7 @@ __global__ void __launch_bounds__(256, 4) linearisation_kernel(const Fr* coef, c
 // ------------------------------------------------------------------------------------------------
 // pack results: [B] proof records (prover.h), plain or compressed
 __global__ void pack_proofs_kernel(const Fq* commit_xy, const ProofState* st, size_t B, uint8_t* out, int compressed) {
+    PLONK_SHORT_KERNEL();
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     if (compressed) {
@@ -345,6 +354,7 @@ __global__ void pack_proofs_kernel(const Fq* commit_xy, const ProofState* st, si
 // filled *bad_input; solve_bad = plonk_prover::solve_bad, or null for a batch that did not come through the solver
 __global__ void pack_status_kernel(const ProofState* st, const uint32_t* closes, const uint8_t* flags, const unsigned long long* bad_input,
                                    size_t bad_stride, const uint32_t* solve_bad, size_t B, uint8_t* out) {
+    PLONK_SHORT_KERNEL();
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     uint8_t f = 0;

@@ -125,6 +125,7 @@ __global__ void blind_h_kernel(const G1Affine* bases, size_t n, G1Affine* htab) 
 // grid (B, count): points first_point .. first_point + count - 1 of every proof record
 __global__ void __launch_bounds__(BLIND_LANES) blind_commit_kernel(const BlindState* bs, const G1Affine* htab, unsigned first_point, size_t B, Fq* commit_xy,
                                                                     uint8_t* flags) {
+    PLONK_SHORT_KERNEL();
     __shared__ G1Xyzz red[BLIND_LANES];
     const size_t b = blockIdx.x;
     const unsigned point = first_point + blockIdx.y, tid = threadIdx.x, term = tid / BLIND_WINDOWS, win = tid % BLIND_WINDOWS;
@@ -178,6 +179,7 @@ __global__ void __launch_bounds__(BLIND_LANES) blind_commit_kernel(const BlindSt
 // Z(w x) is read from the same row one place ahead inside the coset (quotient_kernel), so correcting Z's row corrects both.
 struct BlindZh { Fr v[4]; };
 __global__ void blind_coset_kernel(const BlindState* bs, const Fr* xs, BlindZh zh, unsigned log_n, size_t B, Fr* big) {
+    PLONK_SHORT_KERNEL();
     const size_t n4 = (size_t)4 << log_n, total = B * n4;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n4, k = gI - b * n4;
@@ -202,6 +204,7 @@ __global__ void blind_coset_kernel(const BlindState* bs, const Fr* xs, BlindZh z
 // not read again.  With all blinders zero T_3 is zero and the three slices are quotient_combine_kernel's residues.
 struct BlindCombine { Fr ci, half, g1h, g2h, g3h; };  // i, 1/2, 1 / 2 g^n, 1 / 2 g^2n, 1 / 2 g^3n
 __global__ void blind_combine_kernel(Fr* quot, size_t n, size_t stride, size_t B, BlindCombine k, BlindState* bs) {
+    PLONK_SHORT_KERNEL();
     const size_t total = B * n;
     for (size_t gI = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gI < total; gI += (size_t)gridDim.x * blockDim.x) {
         const size_t b = gI / n, i = gI - b * n;
@@ -229,6 +232,7 @@ __global__ void blind_combine_kernel(Fr* quot, size_t n, size_t stride, size_t B
 // ------------------------------------------------------------------------------------------------
 // Round 4, one lane per proof, behind the evaluation scan: s1_eval, s2_eval and PI(zeta) stay.  (zeta w)^n = zeta^n.
 __global__ void __launch_bounds__(64) blind_evals_kernel(const BlindState* bs, ProofState* st, Fr w, unsigned log_n, size_t B) {
+    PLONK_SHORT_KERNEL();
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const BlindState& s = bs[b];
@@ -245,6 +249,7 @@ __global__ void __launch_bounds__(64) blind_evals_kernel(const BlindState* bs, P
 //     qN = w_Z q_z + w_T1 q_lo + w_T2 q_mid + w_T3 q_hi + v q_a + v^2 q_b + v^3 q_c      (LinWeights order: 5, 7, 8, 9, 10, 11, 12)
 // for W_z and qN = q_z for W_zw; per opening e = qN(x0) and qW = (qN - e) / (X - x0) by synthetic division.  lin_w: [B][15].
 __global__ void __launch_bounds__(64) blind_openings_kernel(BlindState* bs, const ProofState* st, const Fr* lin_w, Fr w, size_t B) {
+    PLONK_SHORT_KERNEL();
     const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     BlindState& s = bs[b];
@@ -274,6 +279,7 @@ __global__ void __launch_bounds__(64) blind_openings_kernel(BlindState* bs, cons
 // W0[i] += e x0^(n - 1 - i) for both openings, behind the division scan: grid (n / (8 x 256), B, 2), eight rows per lane.
 #define BLIND_ROWS_PER_LANE 8
 __global__ void __launch_bounds__(256) blind_division_kernel(const BlindState* bs, const ProofState* st, Fr w, size_t n, size_t B, Fr* wz) {
+    PLONK_SHORT_KERNEL();
     const size_t b = blockIdx.y, z = blockIdx.z;
     const size_t lo = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * BLIND_ROWS_PER_LANE;
     if (lo >= n) return;

@@ -101,9 +101,10 @@ PLONK_DEV Fr gp_chunk_apply(const Fr* NUM, Fr* DEN, Fr* Z, const LaneRange& r, F
 }
 
 // One workgroup per proof.
-__global__ void __launch_bounds__(SCAN_THREADS) grand_product_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
+__global__ void PLONK_BESIDE_ACC(SCAN_THREADS, 4) grand_product_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
                                                                      RoundChallenges direct, size_t n, Fr* z_out,
                                                                      uint32_t* closes, Fr* num_buf, Fr* den_buf) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc_n[SCAN_THREADS], sc_d[SCAN_THREADS];
     __shared__ Fr tot_inv;
     const size_t b = blockIdx.x;
@@ -168,6 +169,7 @@ PLONK_DEV void eval_chunk_sums(Fr (*red)[SCAN_THREADS], const Fr* coef, const Fr
 // One workgroup per proof.
 __global__ void __launch_bounds__(SCAN_THREADS) eval_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, ProofState* st,
                                                             size_t n, size_t B) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr red[NEVAL][SCAN_THREADS];
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x;
@@ -213,6 +215,7 @@ PLONK_DEV void divide_chunk_writeback(const Fr* p, Fr* out, const LaneRange& r, 
 // One workgroup per proof.
 __global__ void __launch_bounds__(SCAN_THREADS) divide_linear_kernel(const Fr* p_in, size_t in_stride, int which,
                                                                      Fr w, const ProofState* st, size_t n, Fr* q_out) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc[SCAN_THREADS];
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x;
@@ -239,6 +242,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) divide_linear_kernel(const Fr* p
 __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_factors_kernel(GrandProductIn in, const Fr* roots, const ProofState* st,
                                                                       RoundChallenges direct, size_t n, Fr* num_buf, Fr* den_buf,
                                                                       Fr* seg_n, Fr* seg_d) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc_n[SCAN_THREADS], sc_d[SCAN_THREADS];
     const size_t b = blockIdx.y;
     const unsigned tid = threadIdx.x, S = gridDim.x;
@@ -263,6 +267,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_factors_kernel(GrandProdu
 // Launch 2 of 3, one workgroup per proof, lane s = segment s: seg_n[s] <- prod of the numerators BEFORE segment s, seg_d[s] <-
 // prod of the denominators AFTER it, tot_inv[b] = the proof's one inversion, closes[b].
 __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_carries_kernel(unsigned S, Fr* seg_n, Fr* seg_d, Fr* tot_inv, uint32_t* closes) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc_n[SCAN_THREADS], sc_d[SCAN_THREADS];
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x;
@@ -285,6 +290,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_carries_kernel(unsigned S
 // Launch 3 of 3, grid (S, B): the lanes' products of the stored factors, scanned and seeded with the segment's carries.
 __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_apply_kernel(size_t n, const Fr* seg_n, const Fr* seg_d, const Fr* tot_inv,
                                                                     const Fr* num_buf, Fr* den_buf, Fr* z_out) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc_n[SCAN_THREADS], sc_d[SCAN_THREADS];
     const size_t b = blockIdx.y;
     const unsigned tid = threadIdx.x, S = gridDim.x;
@@ -311,6 +317,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_apply_kernel(size_t n, co
 // chunk start); the segment's seven sums go to part[b][s][NEVAL].
 __global__ void __launch_bounds__(SCAN_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, const ProofState* st,
                                                                 size_t n, size_t B, Fr* part) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr red[NEVAL][SCAN_THREADS];
     const size_t b = blockIdx.y;
     const unsigned tid = threadIdx.x, S = gridDim.x;
@@ -321,6 +328,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) eval_seg_kernel(const Fr* coef, 
 
 // Launch 2 of 2, one workgroup per proof: lane group p (32 lanes) adds the S partial sums of evaluation p into st[b].evals[p].
 __global__ void __launch_bounds__(SCAN_THREADS) eval_seg_finish_kernel(const Fr* part, unsigned S, ProofState* st) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr red[SCAN_THREADS];
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x, p = tid / 32, l = tid % 32;
@@ -340,6 +348,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) eval_seg_finish_kernel(const Fr*
 struct DivideIn { const Fr* p_in[2]; Fr* q_out[2]; };
 // Launch 1 of 3, grid (S, B, 2): the segment's Horner value H_s = sum_{i in segment} p_i x0^(i - segment start) into seg_h[z][b][s].
 __global__ void __launch_bounds__(SCAN_THREADS) divide_seg_horner_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc[SCAN_THREADS];
     const size_t b = blockIdx.y, B = gridDim.y;
     const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
@@ -359,6 +368,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) divide_seg_horner_kernel(DivideI
 // Launch 2 of 3, grid (B, 1, 2), lane s = segment s: the suffix scan over segments with m = x0^(n / S); seg_h[s] <- the carry
 // entering segment s, q at the segment's last index = sum_{j >= segment end} p_j x0^(j - end).
 __global__ void __launch_bounds__(SCAN_THREADS) divide_seg_carries_kernel(unsigned S, Fr w, const ProofState* st, size_t n, Fr* seg_h) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc[SCAN_THREADS];
     const size_t b = blockIdx.x, B = gridDim.x;
     const unsigned tid = threadIdx.x, z = blockIdx.z;
@@ -373,6 +383,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) divide_seg_carries_kernel(unsign
 // Launch 3 of 3, grid (S, B, 2): the division inside the segment; the segment's carry enters its last lane, as the value one
 // chunk above that lane's rows.
 __global__ void __launch_bounds__(SCAN_THREADS) divide_seg_apply_kernel(DivideIn in, Fr w, const ProofState* st, size_t n, const Fr* seg_h) {
+    PLONK_SHORT_KERNEL();
     __shared__ Fr sc[SCAN_THREADS];
     const size_t b = blockIdx.y, B = gridDim.y;
     const unsigned tid = threadIdx.x, S = gridDim.x, z = blockIdx.z;
