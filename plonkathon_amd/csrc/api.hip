@@ -45,6 +45,15 @@ int ctx_scratch(plonk_ctx* ctx, int slot, size_t bytes, void** out) {
     return PLONK_OK;
 }
 
+int ctx_table_alloc(plonk_ctx* ctx, size_t bytes, size_t entries, void** out) {
+    if (!plonk_dev_malloc(out, bytes ? bytes : 1)) {
+        if (entries) plonk_set_error("hipMalloc of a %zu-entry twiddle table failed", entries);
+        return PLONK_ERR_NOMEM;
+    }
+    ctx->owned.push_back(*out);
+    return PLONK_OK;
+}
+
 int ctx_copy_stream(plonk_ctx* ctx) {
     if (!ctx->copy_stream) PLONK_CHECK_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     return PLONK_OK;
@@ -346,8 +355,7 @@ int plonk_ntt_set_table_budget(plonk_ctx* ctx, size_t bytes) {
 int plonk_fr_ntt(plonk_ctx* ctx, const void* d_in, void* d_out, unsigned log_n, int inverse, size_t batch) {
     PLONK_REQUIRE(ctx && d_in && d_out, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(ctx);
-    const size_t N = (size_t)1 << log_n;
-    return ntt_run(ctx, (const Fr*)d_in, (Fr*)d_out, log_n, inverse != 0, batch, N, N, N, nullptr, nullptr, inverse != 0);
+    return ntt_run(ctx, inverse ? ntt_inverse((const Fr*)d_in, (Fr*)d_out, log_n, batch) : ntt_forward((const Fr*)d_in, (Fr*)d_out, log_n, batch));
 }
 
 int plonk_fr_ntt_dist_columns(plonk_ctx* ctx, const void* d_in, void* d_out, unsigned log_n, unsigned log_world, unsigned rank, int inverse) {
@@ -391,11 +399,14 @@ int plonk_fr_coset_ntt_from_coeffs(plonk_ctx* ctx, const void* d_coeffs, void* d
     PLONK_REQUIRE(ctx && d_coeffs && d_out && offset_le32, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(ctx);
     PLONK_REQUIRE(le32_below_modulus(offset_le32, false), PLONK_ERR_ARG, "offset is not a canonical Fr value");
-    const size_t n = (size_t)1 << log_n, big = n << log_expand;
+    const size_t n = (size_t)1 << log_n;
     const Fr* pw;
     PLONK_TRY(get_power_table(ctx, fr_from_le32(offset_le32), fp_one<FrParams>(), n, &pw));
     // coefficients c_i * offset^i, zero-padded to 2^(log_n+log_expand), forward NTT     poly.py:160-163
-    return ntt_run(ctx, (const Fr*)d_coeffs, (Fr*)d_out, log_n + log_expand, false, batch, n, n, big, pw, nullptr, false);
+    NttCall t = ntt_forward((const Fr*)d_coeffs, (Fr*)d_out, log_n + log_expand, batch);
+    t.in_len = t.in_bstride = n;
+    t.in_scale = pw;
+    return ntt_run(ctx, t);
 }
 
 int plonk_fr_coset_extend(plonk_ctx* ctx, const void* d_in, void* d_out, unsigned log_n,
@@ -406,7 +417,7 @@ int plonk_fr_coset_extend(plonk_ctx* ctx, const void* d_in, void* d_out, unsigne
     void* coeffs;
     PLONK_TRY(ctx_scratch(ctx, 2, batch * n * sizeof(Fr), &coeffs));
     // poly.py:159 — ifft to coefficients first
-    PLONK_TRY(ntt_run(ctx, (const Fr*)d_in, (Fr*)coeffs, log_n, true, batch, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(ntt_run(ctx, ntt_inverse((const Fr*)d_in, (Fr*)coeffs, log_n, batch)));
     return plonk_fr_coset_ntt_from_coeffs(ctx, coeffs, d_out, log_n, 2, offset_le32, batch);
 }
 
@@ -417,14 +428,11 @@ int plonk_fr_coset_to_coeffs(plonk_ctx* ctx, const void* d_in, void* d_out, unsi
     PLONK_REQUIRE(le32_below_modulus(offset_le32, false), PLONK_ERR_ARG, "offset is not a canonical Fr value");
     const size_t M = (size_t)1 << log_m;
     // poly.py:172-176 — ifft, then v_i * (1/offset)^i; the 1/M of the ifft is folded into the table
-    Fr inv_off = fp_inv(fr_from_le32(offset_le32));
-    Fr m_mont = fp_zero<FrParams>();
-    m_mont.v[0] = (uint32_t)M;
-    m_mont.v[1] = (uint32_t)((uint64_t)M >> 32);
-    Fr m_inv = fp_inv(fp_to_mont(m_mont));
     const Fr* pw;
-    PLONK_TRY(get_power_table(ctx, inv_off, m_inv, M, &pw));
-    return ntt_run(ctx, (const Fr*)d_in, (Fr*)d_out, log_m, true, batch, M, M, M, nullptr, pw, false);
+    PLONK_TRY(get_power_table(ctx, fp_inv(fr_from_le32(offset_le32)), host_fp_inv_pow2<FrParams>(log_m), M, &pw));
+    NttCall t{(const Fr*)d_in, (Fr*)d_out, log_m, true, batch};
+    t.out_scale = pw;
+    return ntt_run(ctx, t);
 }
 
 // ---- pointwise ---------------------------------------------------------------------------------
@@ -505,9 +513,7 @@ int plonk_fr_barycentric(plonk_ctx* ctx, const void* d_vals, unsigned log_n, con
     Fr x = fr_from_le32(x_le32);
     PLONK_CHECK_HIP(hipMemcpyAsync(dx, &x, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     PLONK_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    Fr nn = fp_zero<FrParams>();
-    nn.v[0] = (uint32_t)((uint64_t)1 << log_n);
-    Fr n_inv = fp_inv(fp_to_mont(nn));
+    const Fr n_inv = host_fp_inv_pow2<FrParams>(log_n);
     PLONK_TRY(k_fr_barycentric(ctx, (const Fr*)d_vals, roots, log_n, dx, 0, n_inv, dx + 1, 1));
     PLONK_TRY(k_fr_from_mont(ctx, dx + 1, dx + 1, 1));
     PLONK_CHECK_HIP(hipMemcpyAsync(out_le32, dx + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -536,9 +542,7 @@ int plonk_fr_barycentric_many(plonk_ctx* ctx, size_t n_polys, const void* const*
     PLONK_TRY(ctx_scratch(ctx, 2, 32 * sizeof(Fr), &tmp));
     Fr* dx = (Fr*)tmp;
     PLONK_CHECK_HIP(hipMemcpyAsync(dx, xs, n_polys * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    Fr nn = fp_zero<FrParams>();
-    nn.v[0] = (uint32_t)((uint64_t)1 << log_n);
-    const Fr n_inv = fp_inv(fp_to_mont(nn));
+    const Fr n_inv = host_fp_inv_pow2<FrParams>(log_n);
     PLONK_TRY(k_fr_barycentric_ptrs(ctx, polys, roots, log_n, dx, n_inv, dx + 16, n_polys));
     PLONK_TRY(k_fr_from_mont(ctx, dx + 16, dx + 16, n_polys));
     PLONK_CHECK_HIP(hipMemcpyAsync(out_le32, dx + 16, 32 * n_polys, hipMemcpyDeviceToHost, ctx->stream));

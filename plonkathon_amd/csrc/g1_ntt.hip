@@ -130,13 +130,6 @@ __global__ void g1ntt_bitrev_kernel(const G1Xyzz* in, G1Xyzz* out, unsigned log_
     out[i] = in[r];
 }
 
-static Fr g1ntt_fr_u64(uint64_t x) {  // small integer -> Montgomery form (host)
-    Fr a = fp_zero<FrParams>();
-    a.v[0] = (uint32_t)x;
-    a.v[1] = (uint32_t)(x >> 32);
-    return fp_to_mont(a);
-}
-
 // d_bases_out[i] = [L_i(tau)]_1 (affine, Montgomery coordinates, identity = (0, 0)) from the first n = 2^log_n bases of `srs`
 int g1_lagrange_by_ntt(plonk_ctx* ctx, const plonk_srs* srs, unsigned log_n, G1Affine* d_bases_out) {
     const size_t n = (size_t)1 << log_n;
@@ -167,7 +160,7 @@ int g1_lagrange_by_ntt(plonk_ctx* ctx, const plonk_srs* srs, unsigned log_n, G1A
             PLONK_LAUNCH(g1ntt_scalar_mul_kernel, dim3(gb), dim3(G1NTT_BLOCK), 0, ctx->stream, a, n, m, roots, n / (2 * m), 0);
     }
     if (log_n) {  // 1 / n
-        Fr h = fp_inv(g1ntt_fr_u64((uint64_t)n));
+        Fr h = host_fp_inv_pow2<FrParams>(log_n);
         if (hipMemcpyAsync(ninv, &h, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             cleanup();
             plonk_set_error("copy of 1/n failed while building the Lagrange-basis SRS");

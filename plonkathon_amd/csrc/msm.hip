@@ -194,7 +194,7 @@ int msm_lagrange_srs(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, plonk_srs**
     int rc = PLONK_OK;
     for (size_t row0 = 0; row0 < n && rc == PLONK_OK; row0 += rows) {
         PLONK_LAUNCH(fr_identity_rows_kernel, grid1(rows * n), dim3(256), 0, ctx->stream, (Fr*)mat, n, row0, rows);
-        rc = ntt_run(ctx, (const Fr*)mat, (Fr*)mat, log_n, true, rows, n, n, n, nullptr, nullptr, true);
+        rc = ntt_run(ctx, ntt_inverse((const Fr*)mat, (Fr*)mat, log_n, rows));
         if (rc == PLONK_OK) rc = msm_run_device(ctx, srs, (const Fr*)mat, n, rows, n, d_xy, d_fl);
         if (rc == PLONK_OK) {  // canonical x||y -> Montgomery bases; the identity stays (0, 0)
             unsigned g2 = (unsigned)((2 * rows + 255) / 256);

@@ -19,8 +19,6 @@
 
 #include "ntt_wave_host.h"
 
-typedef FpL<FrParams> FrL;
-typedef FpLS<FrParams> FrLS;
 typedef NttWaveT<FrParams> NttWave;
 
 // defaults live in plonk_ctx (ntt_tile_log = 12: 4096 elements = 128 KiB of LDS; ntt_single_log = 11;
@@ -46,6 +44,14 @@ struct NttPass {
     unsigned prev_log_r[3];
 };
 
+// Bytes of LDS of the LDS kernel's tile of R rows by C columns: two 16-byte planes of t_pad elements (rows padded by one in the row
+// pass, as the kernel's row_pitch / t_pad say — written into the kernel through a function they change its code, so they stand there
+// too and the two must agree, or the kernel indexes past its allocation), then the pass's R / 2 small twiddles
+static size_t ntt_tile_shmem(unsigned last, unsigned R, unsigned C) {
+    const size_t t_pad = last ? (size_t)(R + (C > 1 ? 1 : 0)) * C : (size_t)R * C;
+    return 32 * t_pad + 32 * (size_t)(R / 2 ? R / 2 : 1);
+}
+
 PLONK_DEV Fr lds_ld(const u32x4* lo, const u32x4* hi, unsigned i) {
     u32x4 a = lo[i], b = hi[i];
     Fr r;
@@ -68,7 +74,7 @@ __global__ void __launch_bounds__(1024) ntt_pass_radix2_kernel(NttPass p) {
     const unsigned R = 1u << p.log_r, C = 1u << p.log_c;
     const unsigned T = R * C;
     // LDS index of tile element (r, c): column-interleaved for strided passes, padded rows for the
-    // row (last) pass so both the r-fastest and the c-fastest phases are conflict-free.
+    // row (last) pass so both the r-fastest and the c-fastest phases are conflict-free.  (ntt_tile_shmem sizes it)
     const unsigned row_pitch = p.last ? (R + (C > 1 ? 1 : 0)) : 0;
     const unsigned t_pad = p.last ? row_pitch * C : T;
     u32x4* d_lo = reinterpret_cast<u32x4*>(smem);
@@ -264,80 +270,11 @@ __global__ void __launch_bounds__(1024) ntt_pass_radix2_kernel(NttPass p) {
 // ------------------------------------------------------------------------------------------------
 // host side: roots of unity, cached tables, pass planning
 
-static Fr host_fr_from_u64(uint64_t x) {
-    Fr a = fp_zero<FrParams>();
-    a.v[0] = (uint32_t)x;
-    a.v[1] = (uint32_t)(x >> 32);
-    return fp_to_mont(a);
-}
-
 Fr host_root_of_unity(unsigned log_n, bool inverse) {
     Fr w;
     for (int i = 0; i < 8; i++) w.v[i] = inverse ? FrRoots::w28_inv(i) : FrRoots::w28(i);
     for (unsigned i = log_n; i < PLONK_FR_TWO_ADICITY; i++) w = fp_sqr(w);
     return w;
-}
-
-static int alloc_table(plonk_ctx* ctx, size_t n, Fr** out) {
-    void* p = nullptr;
-    if (!plonk_dev_malloc(&p, (n ? n : 1) * sizeof(Fr))) {
-        plonk_set_error("hipMalloc of %zu-entry twiddle table failed", n);
-        return PLONK_ERR_NOMEM;
-    }
-    ctx->owned.push_back(p);
-    *out = (Fr*)p;
-    return PLONK_OK;
-}
-
-static int get_small_tw(plonk_ctx* ctx, unsigned log_r, bool inverse, const Fr** out) {
-    unsigned key = log_r | (inverse ? 256u : 0u);
-    auto it = ctx->tw.small.find(key);
-    if (it == ctx->tw.small.end()) {
-        Fr* t;
-        size_t n = log_r ? ((size_t)1 << (log_r - 1)) : 1;
-        PLONK_TRY(alloc_table(ctx, n, &t));
-        PLONK_TRY(k_fr_powers(ctx, host_root_of_unity(log_r, inverse), fp_one<FrParams>(), t, n));
-        it = ctx->tw.small.emplace(key, t).first;
-    }
-    *out = it->second;
-    return PLONK_OK;
-}
-
-static int get_lo_hi(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** lo, const Fr** hi) {
-    unsigned key = log_n | (inverse ? 256u : 0u);
-    auto it = ctx->tw.lo.find(key);
-    if (it == ctx->tw.lo.end()) {
-        Fr w = host_root_of_unity(log_n, inverse);
-        unsigned log_lo = log_n < NTT_TW_LO_LOG ? log_n : NTT_TW_LO_LOG;
-        Fr *tl, *th;
-        PLONK_TRY(alloc_table(ctx, (size_t)1 << log_lo, &tl));
-        PLONK_TRY(k_fr_powers(ctx, w, fp_one<FrParams>(), tl, (size_t)1 << log_lo));
-        size_t nhi = log_n > NTT_TW_LO_LOG ? ((size_t)1 << (log_n - NTT_TW_LO_LOG)) : 1;
-        Fr whi = w;
-        for (unsigned i = 0; i < NTT_TW_LO_LOG; i++) whi = fp_sqr(whi);
-        PLONK_TRY(alloc_table(ctx, nhi, &th));
-        PLONK_TRY(k_fr_powers(ctx, whi, fp_one<FrParams>(), th, nhi));
-        ctx->tw.lo.emplace(key, tl);
-        ctx->tw.hi.emplace(key, th);
-        it = ctx->tw.lo.find(key);
-    }
-    *lo = it->second;
-    *hi = ctx->tw.hi[key];
-    return PLONK_OK;
-}
-
-// full table w^0 .. w^(N-1) (barycentric evaluation, permutation argument)
-int ntt_get_roots(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** out) {
-    unsigned key = log_n | (inverse ? 256u : 0u);
-    auto it = ctx->tw.full.find(key);
-    if (it == ctx->tw.full.end()) {
-        Fr* t;
-        PLONK_TRY(alloc_table(ctx, (size_t)1 << log_n, &t));
-        PLONK_TRY(k_fr_powers(ctx, host_root_of_unity(log_n, inverse), fp_one<FrParams>(), t, (size_t)1 << log_n));
-        it = ctx->tw.full.emplace(key, t).first;
-    }
-    *out = it->second;
-    return PLONK_OK;
 }
 
 // pass radices, most significant digit first
@@ -381,16 +318,119 @@ bool ntt_wave_plan(const plonk_ctx* ctx, unsigned log_n, bool latency, unsigned*
 struct Bn254FrField {
     typedef FrParams P;
     static Fr root_of_unity(unsigned log_n, bool inverse) { return host_root_of_unity(log_n, inverse); }
-    static Fr from_u64(uint64_t x) { return host_fr_from_u64(x); }
     static int packed_roots(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** out) { return ntt_get_roots(ctx, log_n, inverse, out); }
-    static int packed_lo_hi(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** lo, const Fr** hi) { return get_lo_hi(ctx, log_n, inverse, lo, hi); }
+    static int packed_lo_hi(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** lo, const Fr** hi) {
+        return wave_packed_lo_hi<Bn254FrField>(ctx, ctx->tw.lo, ctx->tw.hi, log_n, inverse, lo, hi);
+    }
     static int powers(plonk_ctx* ctx, const Fr& base, const Fr& first, Fr* out, size_t n) { return k_fr_powers(ctx, base, first, out, n); }
     static WaveTables& tables(plonk_ctx* ctx) { return ctx->tw.wave; }
 };
 
-static int ntt_run_wave(plonk_ctx* ctx, const Fr* in, Fr* out, unsigned log_n, bool inverse, size_t batch, size_t in_len,
-                        size_t in_bstride, size_t out_bstride, const Fr* in_scale, const Fr* out_scale, bool scale_by_n_inv, const NttFan* fan) {
-    return wave_run<Bn254FrField>(ctx, in, out, log_n, inverse, batch, in_len, in_bstride, out_bstride, in_scale, out_scale, scale_by_n_inv, fan);
+// full table w^0 .. w^(N-1) (barycentric evaluation, permutation argument)
+int ntt_get_roots(plonk_ctx* ctx, unsigned log_n, bool inverse, const Fr** out) {
+    return wave_root_powers<Bn254FrField>(ctx, ctx->tw.full, ntt_key(log_n, inverse), log_n, inverse, 0, (size_t)1 << log_n, out);
+}
+// w_R^k, k < R/2: a pass's LDS twiddles
+static int get_small_tw(plonk_ctx* ctx, unsigned log_r, bool inverse, const Fr** out) {
+    return wave_root_powers<Bn254FrField>(ctx, ctx->tw.small, ntt_key(log_r, inverse), log_r, inverse, 0, log_r ? (size_t)1 << (log_r - 1) : 1, out);
+}
+
+// ---- the engine's entry: one call, on the wave kernels or on the LDS kernel ----------------------------------------------------
+int ntt_run(plonk_ctx* ctx, const NttCall& call) {
+    const unsigned log_n = call.log_n;
+    PLONK_REQUIRE(log_n <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "NTT size 2^%u exceeds the 2-adicity (28) of BN254 Fr", log_n);
+    const NttCall t = ntt_call_resolved(call);
+    const size_t batch = t.batch, N = (size_t)1 << log_n;
+    if (!batch) return PLONK_OK;
+    unsigned wr2 = 0;
+    const bool wave_ok = ntt_policy_wave(ctx, log_n, &wr2);
+    if (t.fan.count > 1 && !(wave_ok && !wr2 && wave_fan_ok(t.fan, N, t.out_scale != nullptr))) {  // no single launch for this size / kernel choice: one call per copy
+        NttCall one = t;
+        one.fan = NttFan{};
+        for (unsigned f = 0; f < t.fan.count; f++) {
+            PLONK_TRY(ntt_run(ctx, one));
+            one.in += t.fan.in_stride;
+            one.out += t.fan.out_stride;
+            if (one.in_scale) one.in_scale += t.fan.scale_stride;
+            if (one.out_scale) one.out_scale += t.fan.scale_stride;
+        }
+        return PLONK_OK;
+    }
+    if (wave_ok) return wave_run<Bn254FrField>(ctx, t);  // (ntt_wave_host.h: the policy)
+    PLONK_REQUIRE(batch <= 65535, PLONK_ERR_ARG, "NTT batch %zu exceeds 65535", batch);
+    unsigned radices[4];
+    const unsigned P = plan_passes(ctx, log_n, radices);
+    PLONK_REQUIRE(P <= 4, PLONK_ERR_ARG, "NTT of size 2^%u needs %u passes at radix 2^%u (max 4)", log_n, P, ctx->ntt_radix_log);
+
+    void* tmpv = nullptr;  // the inter-pass buffer and twiddles of a multi-pass plan
+    const Fr *lo = nullptr, *hi = nullptr;
+    if (P > 1) {
+        PLONK_TRY(ctx_scratch(ctx, 0, batch * N * sizeof(Fr), &tmpv));
+        PLONK_TRY(Bn254FrField::packed_lo_hi(ctx, log_n, t.inverse, &lo, &hi));
+    }
+    Fr* tmp = (Fr*)tmpv;
+
+    unsigned log_h = 0;
+    for (unsigned pi = 0; pi < P; pi++) {
+        NttPass p;
+        memset(&p, 0, sizeof p);
+        const bool first = pi == 0, last = pi == P - 1;
+        p.in = first ? t.in : tmp;
+        p.out = last ? t.out : tmp;
+        p.in_bstride = first ? t.in_bstride : N;
+        p.out_bstride = last ? t.out_bstride : N;
+        p.log_n = log_n;
+        p.log_r = radices[pi];
+        p.log_h = log_h;
+        p.log_s = log_n - log_h - p.log_r;
+        p.first = first;
+        p.last = last;
+        p.in_len = (unsigned)(t.in_len < N ? t.in_len : N);
+        // three-pass transforms (N >= 2^21) run faster with 2048-element tiles (two workgroups per CU):
+        // measured 2.40 ms vs 2.90 ms at 2^24 (profiles/r01_h_sweep.jsonl); 2^12..2^20 prefer 4096
+        unsigned tile_log = (ctx->ntt_tile_log == 12 && P >= 3) ? 11 : ctx->ntt_tile_log;
+        // small jobs: shrink the tile until the pass has >= 512 workgroups (two per CU) or one column per tile — a lone
+        // 2^16 transform used to run on 16 workgroups of 4096 elements.  Narrow tiles give up 128-byte chunks, but such
+        // a job's data (<= 32 MiB) sits in L2 / MALL anyway.
+        // Measured (profiles/r02_h_ntt_adaptive_tiles.json): 2^16 0.096 -> 0.042 ms, 2^14 0.088 -> 0.040, 2^18 0.113 -> 0.075,
+        // 2^19 0.122 -> 0.087; from 2^20 elements up the 4096-element tiles win (2^20: 0.139 vs 0.151 ms).
+        if (ctx->ntt_tile_log == 12 && ctx->ntt_adaptive_tiles && ((size_t)batch << log_n) < ((size_t)1 << 20))
+            while (tile_log > p.log_r && (((size_t)batch << log_n) >> tile_log) < 512) tile_log--;
+        unsigned log_c = tile_log > p.log_r ? tile_log - p.log_r : 0;
+        unsigned avail = last ? (P > 1 ? radices[0] : 0) : p.log_s;
+        if (log_c > avail) log_c = avail;
+        p.log_c = log_c;
+        PLONK_TRY(get_small_tw(ctx, p.log_r, t.inverse, &p.small_tw));
+        p.tw_lo = lo;
+        p.tw_hi = hi;
+        p.in_scale = first ? t.in_scale : nullptr;
+        p.out_scale = last ? t.out_scale : nullptr;
+        if (last && t.scale_by_n_inv) {
+            p.out_scalar = host_fp_inv_pow2<FrParams>(log_n);
+            p.has_out_scalar = 1;
+        }
+        p.nprev = last ? pi : 0;
+        for (unsigned q = 0; q < pi && q < 3; q++) p.prev_log_r[q] = radices[q];
+
+        const unsigned R = 1u << p.log_r, C = 1u << p.log_c, T = R * C;
+        unsigned nthr = T / 4;
+        if (nthr < 64) nthr = 64;
+        if (nthr > 1024u) nthr = 1024;
+        const size_t shmem = ntt_tile_shmem(last, R, C);
+        const size_t tiles = N / T;
+        if (!ctx->ntt_attr_set) {  // a per-device attribute: tracked per context, not per process
+            PLONK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_radix2_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+            ctx->ntt_attr_set = true;
+        }
+        // algorithmic bytes of a size-N transform: 64 * N (read once, write once), split over its passes
+        PLONK_TRY(prof_begin(ctx, "ntt_pass", 64.0 * (double)N * (double)batch / (double)P));
+        PLONK_LAUNCH(ntt_pass_radix2_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(nthr), shmem, ctx->stream, p);
+        PLONK_TRY(prof_end(ctx));
+        PLONK_CHECK_HIP(hipGetLastError());
+        log_h += p.log_r;
+    }
+    return PLONK_OK;
 }
 
 // ---- distributed four-step transform: the two local steps (the all-to-all between them is comm.hip's) ------------------
@@ -409,14 +449,12 @@ int ntt_dist_plan(unsigned log_n, unsigned log_w, unsigned* log_r1, unsigned* lo
     return PLONK_OK;
 }
 
-static void ntt_wave_consts(NttWave* p, unsigned log_n, bool inverse) { wave_params_init<Bn254FrField>(p, log_n, inverse); }
-
 int ntt_dist_columns(plonk_ctx* ctx, const Fr* in, Fr* out, unsigned log_n, unsigned log_w, unsigned rank, bool inverse) {
     unsigned log_r1, log_r2;
     PLONK_TRY(ntt_dist_plan(log_n, log_w, &log_r1, &log_r2));
     const unsigned log_cl = log_r2 - log_w;
     NttWave a;
-    ntt_wave_consts(&a, log_n, inverse);
+    wave_params_init<Bn254FrField>(&a, log_n, inverse);
     PLONK_TRY(wave_lo_hi<Bn254FrField>(ctx, log_n, inverse, false, &a.tw_lo, &a.tw_hi));
     PLONK_TRY(wave_program_table<Bn254FrField>(ctx, log_r1, wavel_log_e(log_r1), inverse, &a.roots));
     a.mode = 1;
@@ -438,7 +476,7 @@ int ntt_dist_rows(plonk_ctx* ctx, const Fr* in, Fr* out, unsigned log_n, unsigne
     PLONK_TRY(ntt_dist_plan(log_n, log_w, &log_r1, &log_r2));
     const unsigned log_cl = log_r2 - log_w, log_kl = log_r1 - log_w;
     NttWave c;
-    ntt_wave_consts(&c, log_n, inverse);
+    wave_params_init<Bn254FrField>(&c, log_n, inverse);
     PLONK_TRY(wave_program_table<Bn254FrField>(ctx, log_r2, wavel_log_e(log_r2), inverse, &c.roots));
     c.mode = 2;
     c.log_other = log_kl;  // output stride: frequency k2 of local row kl at out[k2 * R1/W + kl]
@@ -450,114 +488,12 @@ int ntt_dist_rows(plonk_ctx* ctx, const Fr* in, Fr* out, unsigned log_n, unsigne
     c.out = out;
     c.in_len = 1u << (log_n - log_w);
     if (inverse) {
-        c.out_scalar = fp_inv(host_fr_from_u64((uint64_t)1 << log_n));
+        c.out_scalar = host_fp_inv_pow2<FrParams>(log_n);
         c.has_out_scalar = 1;
     }
     PLONK_TRY(prof_begin(ctx, "ntt_pass", 32.0 * (double)((size_t)1 << (log_n - log_w))));
     PLONK_TRY(wave_launch<Bn254FrField>(ctx, c, log_r2, wavel_log_e(log_r2), 1u << log_kl, 1));
     PLONK_TRY(prof_end(ctx));
     PLONK_CHECK_HIP(hipGetLastError());
-    return PLONK_OK;
-}
-
-int ntt_run(plonk_ctx* ctx, const Fr* in, Fr* out, unsigned log_n, bool inverse, size_t batch, size_t in_len,
-            size_t in_bstride, size_t out_bstride, const Fr* in_scale, const Fr* out_scale, bool scale_by_n_inv, const NttFan* fan) {
-    PLONK_REQUIRE(log_n <= PLONK_FR_TWO_ADICITY, PLONK_ERR_ARG, "NTT size 2^%u exceeds the 2-adicity (28) of BN254 Fr", log_n);
-    if (!batch) return PLONK_OK;
-    const size_t N = (size_t)1 << log_n;
-    unsigned wr1, wr2;
-    if (fan && fan->count <= 1) fan = nullptr;
-    const bool wave_ok = (ctx->ntt_kind == 0 || ctx->ntt_kind >= 5) && ntt_wave_plan(ctx, log_n, false, &wr1, &wr2) &&
-                         ((ctx->ntt_single_log >= 11 && ctx->ntt_radix_log >= 10) || ctx->ntt_kind >= 5);
-    if (fan && !(wave_ok && !wr2 && wave_fan_ok(*fan, N, out_scale != nullptr))) {  // no single launch for this size / kernel choice: one call per copy
-        for (unsigned f = 0; f < fan->count; f++)
-            PLONK_TRY(ntt_run(ctx, in + (size_t)f * fan->in_stride, out + (size_t)f * fan->out_stride, log_n, inverse, batch, in_len, in_bstride, out_bstride,
-                              in_scale ? in_scale + (size_t)f * fan->scale_stride : nullptr, out_scale ? out_scale + (size_t)f * fan->scale_stride : nullptr,
-                              scale_by_n_inv, nullptr));
-        return PLONK_OK;
-    }
-    // The wave kernels serve every size they cover (2^7 .. 2^13 in one launch, 2^14 .. 2^26 in two): measured on MI355X
-    // they beat the LDS kernels at every such size and batch (profiles/r02_e_ntt_kinds.json, r02_v_ntt_kinds.json, r03_*;
-    // 2^14 / 2^15 since round 4's two-element kernels).  kind 4 = automatic choice among the LDS kernels only (A/B runs); a
-    // plonk_ntt_configure with small tiles (the multi-pass tests) also keeps a transform on the LDS kernels.
-    if (wave_ok) return ntt_run_wave(ctx, in, out, log_n, inverse, batch, in_len, in_bstride, out_bstride, in_scale, out_scale, scale_by_n_inv, fan);
-    PLONK_REQUIRE(batch <= 65535, PLONK_ERR_ARG, "NTT batch %zu exceeds 65535", batch);
-    unsigned radices[4];
-    const unsigned P = plan_passes(ctx, log_n, radices);
-    PLONK_REQUIRE(P <= 4, PLONK_ERR_ARG, "NTT of size 2^%u needs %u passes at radix 2^%u (max 4)", log_n, P, ctx->ntt_radix_log);
-
-    Fr* tmp = nullptr;
-    if (P > 1) {
-        void* s;
-        PLONK_TRY(ctx_scratch(ctx, 0, batch * N * sizeof(Fr), &s));
-        tmp = (Fr*)s;
-    }
-    const Fr *lo = nullptr, *hi = nullptr;
-    if (P > 1) PLONK_TRY(get_lo_hi(ctx, log_n, inverse, &lo, &hi));
-
-    unsigned log_h = 0;
-    for (unsigned pi = 0; pi < P; pi++) {
-        NttPass p;
-        memset(&p, 0, sizeof p);
-        const bool first = pi == 0, last = pi == P - 1;
-        p.in = first ? in : tmp;
-        p.out = last ? out : tmp;
-        p.in_bstride = first ? in_bstride : N;
-        p.out_bstride = last ? out_bstride : N;
-        p.log_n = log_n;
-        p.log_r = radices[pi];
-        p.log_h = log_h;
-        p.log_s = log_n - log_h - p.log_r;
-        p.first = first;
-        p.last = last;
-        p.in_len = (unsigned)(in_len < N ? in_len : N);
-        // three-pass transforms (N >= 2^21) run faster with 2048-element tiles (two workgroups per CU):
-        // measured 2.40 ms vs 2.90 ms at 2^24 (profiles/r01_h_sweep.jsonl); 2^12..2^20 prefer 4096
-        unsigned tile_log = (ctx->ntt_tile_log == 12 && P >= 3) ? 11 : ctx->ntt_tile_log;
-        // small jobs: shrink the tile until the pass has >= 512 workgroups (two per CU) or one column per tile — a lone
-        // 2^16 transform used to run on 16 workgroups of 4096 elements.  Narrow tiles give up 128-byte chunks, but such
-        // a job's data (<= 32 MiB) sits in L2 / MALL anyway.
-        // Measured (profiles/r02_h_ntt_adaptive_tiles.json): 2^16 0.096 -> 0.042 ms, 2^14 0.088 -> 0.040, 2^18 0.113 -> 0.075,
-        // 2^19 0.122 -> 0.087; from 2^20 elements up the 4096-element tiles win (2^20: 0.139 vs 0.151 ms).
-        if (ctx->ntt_tile_log == 12 && ctx->ntt_adaptive_tiles && ((size_t)batch << log_n) < ((size_t)1 << 20))
-            while (tile_log > p.log_r && (((size_t)batch << log_n) >> tile_log) < 512) tile_log--;
-        unsigned log_c = tile_log > p.log_r ? tile_log - p.log_r : 0;
-        unsigned avail = last ? (P > 1 ? radices[0] : 0) : p.log_s;
-        if (log_c > avail) log_c = avail;
-        p.log_c = log_c;
-        PLONK_TRY(get_small_tw(ctx, p.log_r, inverse, &p.small_tw));
-        p.tw_lo = lo;
-        p.tw_hi = hi;
-        p.in_scale = first ? in_scale : nullptr;
-        p.out_scale = last ? out_scale : nullptr;
-        if (last && scale_by_n_inv) {
-            Fr nn = host_fr_from_u64((uint64_t)N);
-            p.out_scalar = fp_inv(nn);
-            p.has_out_scalar = 1;
-        }
-        p.nprev = last ? pi : 0;
-        for (unsigned q = 0; q < pi && q < 3; q++) p.prev_log_r[q] = radices[q];
-
-        const unsigned R = 1u << p.log_r, C = 1u << p.log_c, T = R * C;
-        unsigned nthr = T / 4;
-        if (nthr < 64) nthr = 64;
-        if (nthr > 1024u) nthr = 1024;
-        const unsigned row_pitch = last ? (R + (C > 1 ? 1 : 0)) : 0;
-        const size_t t_pad = last ? (size_t)row_pitch * C : T;
-        const size_t tw_bytes = 32 * (size_t)(R / 2 ? R / 2 : 1);
-        const size_t shmem = 32 * t_pad + tw_bytes;
-        const size_t tiles = N / T;
-        if (!ctx->ntt_attr_set) {  // a per-device attribute: tracked per context, not per process
-            PLONK_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ntt_pass_radix2_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-            ctx->ntt_attr_set = true;
-        }
-        // algorithmic bytes of a size-N transform: 64 * N (read once, write once), split over its passes
-        PLONK_TRY(prof_begin(ctx, "ntt_pass", 64.0 * (double)N * (double)batch / (double)P));
-        PLONK_LAUNCH(ntt_pass_radix2_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(nthr), shmem, ctx->stream, p);
-        PLONK_TRY(prof_end(ctx));
-        PLONK_CHECK_HIP(hipGetLastError());
-        log_h += p.log_r;
-    }
     return PLONK_OK;
 }

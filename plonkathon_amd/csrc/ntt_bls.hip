@@ -65,42 +65,15 @@ static BlsFr bls_root_of_unity(unsigned log_n, bool inverse) {
     return w;
 }
 
-// a cached table of powers of a root (the packed source of a limb table; kept: the conversion kernel reads it asynchronously)
-static int bls_power_table(plonk_ctx* ctx, std::map<unsigned, void*>& cache, unsigned key, const BlsFr& base, size_t n, const BlsFr** out) {
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-        void* d = nullptr;
-        if (!plonk_dev_malloc(&d, n * sizeof(BlsFr))) {
-            plonk_set_error("hipMalloc of a %zu-entry twiddle table failed", n);
-            return PLONK_ERR_NOMEM;
-        }
-        ctx->owned.push_back(d);
-        PLONK_TRY(bls_powers(ctx, base, fp_one<BlsFrParams>(), (BlsFr*)d, n));
-        it = cache.emplace(key, d).first;
-    }
-    *out = (const BlsFr*)it->second;
-    return PLONK_OK;
-}
-
 struct BlsFrField {
     typedef BlsFrParams P;
     static BlsFr root_of_unity(unsigned log_n, bool inverse) { return bls_root_of_unity(log_n, inverse); }
-    static BlsFr from_u64(uint64_t x) {
-        BlsFr a = fp_zero<BlsFrParams>();
-        a.v[0] = (uint32_t)x;
-        a.v[1] = (uint32_t)(x >> 32);
-        return fp_to_mont(a);
-    }
+    // the packed sources of the limb tables are kept: the conversion kernels read them asynchronously
     static int packed_roots(plonk_ctx* ctx, unsigned log_n, bool inverse, const BlsFr** out) {
-        return bls_power_table(ctx, ctx->wave_bls.packed[0], log_n | (inverse ? 256u : 0u), bls_root_of_unity(log_n, inverse), (size_t)1 << log_n, out);
+        return wave_root_powers<BlsFrField>(ctx, ctx->wave_bls.packed[0], ntt_key(log_n, inverse), log_n, inverse, 0, (size_t)1 << log_n, out);
     }
     static int packed_lo_hi(plonk_ctx* ctx, unsigned log_n, bool inverse, const BlsFr** lo, const BlsFr** hi) {
-        const unsigned key = log_n | (inverse ? 256u : 0u), log_lo = log_n < NTT_TW_LO_LOG ? log_n : NTT_TW_LO_LOG;
-        const BlsFr w = bls_root_of_unity(log_n, inverse);
-        BlsFr whi = w;
-        for (unsigned i = 0; i < NTT_TW_LO_LOG; i++) whi = fp_sqr(whi);
-        PLONK_TRY(bls_power_table(ctx, ctx->wave_bls.packed[1], key, w, (size_t)1 << log_lo, lo));
-        return bls_power_table(ctx, ctx->wave_bls.packed[2], key, whi, log_n > NTT_TW_LO_LOG ? (size_t)1 << (log_n - NTT_TW_LO_LOG) : 1, hi);
+        return wave_packed_lo_hi<BlsFrField>(ctx, ctx->wave_bls.packed[1], ctx->wave_bls.packed[2], log_n, inverse, lo, hi);
     }
     static int powers(plonk_ctx* ctx, const BlsFr& base, const BlsFr& first, BlsFr* out, size_t n) { return bls_powers(ctx, base, first, out, n); }
     static WaveTables& tables(plonk_ctx* ctx) { return ctx->wave_bls; }
@@ -192,13 +165,16 @@ int plonk_bls_fr_coset_extend(plonk_ctx* ctx, const void* d_in, void* d_out, uns
     PLONK_REQUIRE(bls_from_le32(offset_le32, &off), PLONK_ERR_ARG, "offset is not a canonical BLS12-381 Fr value");
     PLONK_REQUIRE(bls_size_ok(ctx, log_n) && bls_size_ok(ctx, log_n + 2), PLONK_ERR_ARG,
                   "the BLS12-381 coset extension covers 2^8 .. 2^24 values (4n <= 2^26), not 2^%u", log_n);
-    const size_t n = (size_t)1 << log_n, big = n << 2;
+    const size_t n = (size_t)1 << log_n;
     void* coeffs;
     PLONK_TRY(ctx_scratch(ctx, 2, batch * n * sizeof(BlsFr), &coeffs));
-    PLONK_TRY(wave_run<BlsFrField>(ctx, (const BlsFr*)d_in, (BlsFr*)coeffs, log_n, true, batch, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(wave_run<BlsFrField>(ctx, ntt_inverse((const BlsFr*)d_in, (BlsFr*)coeffs, log_n, batch)));
     const BlsFr* pw;
     PLONK_TRY(bls_power_table(ctx, off, fp_one<BlsFrParams>(), n, &pw));
-    return wave_run<BlsFrField>(ctx, (const BlsFr*)coeffs, (BlsFr*)d_out, log_n + 2, false, batch, n, n, big, pw, nullptr, false);
+    NttCallT<BlsFr> t = ntt_forward((const BlsFr*)coeffs, (BlsFr*)d_out, log_n + 2, batch);
+    t.in_len = t.in_bstride = n;
+    t.in_scale = pw;
+    return wave_run<BlsFrField>(ctx, t);
 }
 
 // poly.py:169-177 over this field: M coset values -> ifft -> v_i (1/offset)^i; the 1/M of the ifft rides in the power table
@@ -211,19 +187,19 @@ int plonk_bls_fr_coset_to_coeffs(plonk_ctx* ctx, const void* d_in, void* d_out, 
     PLONK_REQUIRE(bls_size_ok(ctx, log_m), PLONK_ERR_ARG, "the BLS12-381 transform covers 2^8 .. 2^26 points (the wave kernels' sizes), not 2^%u", log_m);
     const size_t M = (size_t)1 << log_m;
     const BlsFr* pw;
-    PLONK_TRY(bls_power_table(ctx, fp_inv(off), fp_inv(BlsFrField::from_u64((uint64_t)M)), M, &pw));
-    return wave_run<BlsFrField>(ctx, (const BlsFr*)d_in, (BlsFr*)d_out, log_m, true, batch, M, M, M, nullptr, pw, false);
+    PLONK_TRY(bls_power_table(ctx, fp_inv(off), host_fp_inv_pow2<BlsFrParams>(log_m), M, &pw));
+    NttCallT<BlsFr> t{(const BlsFr*)d_in, (BlsFr*)d_out, log_m, true, batch};
+    t.out_scale = pw;
+    return wave_run<BlsFrField>(ctx, t);
 }
 
 int plonk_bls_fr_ntt(plonk_ctx* ctx, const void* d_in, void* d_out, unsigned log_n, int inverse, size_t batch) {
     PLONK_REQUIRE(ctx && d_in && d_out, PLONK_ERR_ARG, "bad argument");
     PLONK_ENTER(ctx);
     if (!batch) return PLONK_OK;
-    unsigned r1, r2;
-    PLONK_REQUIRE(ntt_wave_plan(ctx, log_n, false, &r1, &r2), PLONK_ERR_ARG,
-                  "the BLS12-381 transform covers 2^8 .. 2^26 points (the wave kernels' sizes), not 2^%u", log_n);
-    const size_t N = (size_t)1 << log_n;
-    return wave_run<BlsFrField>(ctx, (const BlsFr*)d_in, (BlsFr*)d_out, log_n, inverse != 0, batch, N, N, N, nullptr, nullptr, inverse != 0);
+    PLONK_REQUIRE(bls_size_ok(ctx, log_n), PLONK_ERR_ARG, "the BLS12-381 transform covers 2^8 .. 2^26 points (the wave kernels' sizes), not 2^%u", log_n);
+    const BlsFr* in = (const BlsFr*)d_in;
+    return wave_run<BlsFrField>(ctx, inverse ? ntt_inverse(in, (BlsFr*)d_out, log_n, batch) : ntt_forward(in, (BlsFr*)d_out, log_n, batch));
 }
 
 }  // extern "C"

@@ -2,9 +2,9 @@
 // one- / two-pass driver.  A field is a traits type F with
 //   typedef ... P;                                            the Montgomery parameters (fp.h)
 //   static Fp<P> root_of_unity(unsigned log_n, bool inverse)  w = g^((m-1)/2^log_n), Montgomery form (host)
-//   static Fp<P> from_u64(uint64_t)                           Montgomery form of a small integer (host)
 //   static int packed_roots(ctx, log_n, inverse, const Fp<P>** out)            w^k, k < 2^log_n, on the device
 //   static int packed_lo_hi(ctx, log_n, inverse, const Fp<P>** lo, const Fp<P>** hi)   w^e = lo[e & 1023] * hi[e >> 10]
+//                                                             (both: wave_root_powers / wave_packed_lo_hi over the field's own maps)
 //   static int powers(ctx, base, first, Fp<P>* out, n)        out[i] = first * base^i on the device
 //   static WaveTables& tables(plonk_ctx*)                     this field's table cache of the context
 // ntt.hip instantiates it for BN254 Fr (the prover's field), ntt_bls.hip for BLS12-381 Fr (standalone transform).
@@ -17,18 +17,91 @@
 // the two-pass plan of a size (ntt.hip; field independent)
 bool ntt_wave_plan(const plonk_ctx* ctx, unsigned log_n, bool latency, unsigned* log_r1, unsigned* log_r2);
 
+// ---- which kernel, which form: the whole policy ---------------------------------------------------------------------------
+// plonk_ctx::ntt_kind, as plonk_ntt_select_kernel numbers it (2 and 3 are no kinds)
+enum NttKind : unsigned {
+    NTT_KIND_AUTO = 0,             // the wave kernels where they apply, else the LDS kernel
+    NTT_KIND_LDS = 1,              // the LDS kernel
+    NTT_KIND_LDS_AUTO = 4,         // the automatic choice among the LDS kernels only (A/B runs): the same kernel
+    NTT_KIND_WAVE = 5,             // from here up: the wave kernels wherever they apply, whatever plonk_ntt_configure says
+    NTT_KIND_WAVE_NO_LATENCY = 6,  // ... never the two-element latency forms, and every call counts as big (tests, A/B runs)
+    NTT_KIND_WAVE_LATENCY = 7,     // ... the latency forms wherever they exist
+    NTT_KIND_WAVE_W12_1024 = 8,    // ... 2^12 on its 1024-thread form everywhere
+};
+static inline int wave_env_int(const char* name, int unset) {  // an A/B switch of the environment
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+}
+// Does a BN254 transform of 2^log_n go to the wave kernels (*log_r2: 0 = in one launch)?  They serve every size they cover
+// (2^7 .. 2^13 in one launch, 2^14 .. 2^26 in two): measured on MI355X they beat the LDS kernels at every such size and batch
+// (profiles/r02_e_ntt_kinds.json, r02_v_ntt_kinds.json, r03_*; 2^14 / 2^15 since round 4's two-element kernels).  A
+// plonk_ntt_configure with small tiles (the multi-pass tests) keeps a transform on the LDS kernels unless the kind forces waves.
+static inline bool ntt_policy_wave(const plonk_ctx* ctx, unsigned log_n, unsigned* log_r2) {
+    const bool forced = ctx->ntt_kind >= NTT_KIND_WAVE;
+    unsigned log_r1;
+    return (ctx->ntt_kind == NTT_KIND_AUTO || forced) && ntt_wave_plan(ctx, log_n, false, &log_r1, log_r2) &&
+           ((ctx->ntt_single_log >= 11 && ctx->ntt_radix_log >= 10) || forced);
+}
+// The form of a wave-kernel call from its element count, as ntt_key flags (a WavePlan is cached per form):
+//   FULL       the column pass on the full inter-pass table (profiles/r03_m_ntt_sweep.jsonl: the table wins 4-10 % wherever the
+//              column pass fills the chip; a lone 2^18 — one workgroup per CU, every load latency exposed — is 5 % faster on the
+//              small, L2-resident tables)
+//   LATENCY    a small job (<= 2^18 elements) waits for one wave's instruction chain: the two-element forms
+//   BIG        at least 2^20 elements: the 512-thread form of 2^12 pays from there (profiles/r04_f_ntt_2e12_forms_ab.jsonl)
+static inline unsigned ntt_policy_form(const plonk_ctx* ctx, unsigned log_n, size_t batch) {
+    const size_t elems = batch << log_n;
+    const unsigned kind = ctx->ntt_kind;
+    const bool full = log_n >= 14 && (log_n <= 16 || elems >= ((size_t)1 << 19));
+    const bool latency = kind == NTT_KIND_WAVE_NO_LATENCY ? false : (kind == NTT_KIND_WAVE_LATENCY || elems <= ((size_t)1 << 18));
+    const bool big = kind == NTT_KIND_WAVE_NO_LATENCY || elems >= ((size_t)1 << 20);
+    return (full ? NTT_KEY_FULL : 0u) | (latency ? NTT_KEY_LATENCY : 0u) | (big ? NTT_KEY_BIG : 0u);
+}
+// 2^12 runs as 512 threads x 8 elements (two workgroups per CU) as a single pass and as a row pass of big calls: 18.0 -> 19.2 G
+// elements/s at 512 transforms, 17.7 -> 20.7 at 4096, row passes +2 .. 5 %; a small call is faster on the 1024-thread kernel's
+// shorter chain (a lone 2^12: 0.043 against 0.048 ms).  A column pass stays on the 1024-thread 4-element kernel (the one-table
+// inter-pass twiddles need its register room; ntt_wave.h)
+static inline bool ntt_policy_w12_as_512x8(const plonk_ctx* ctx, bool big) {
+    static const bool env_on = wave_env_int("PLONK_NTT_W12", 0) != 4;  // PLONK_NTT_W12 = 4: 2^12 on the 1024-thread 4-element kernel everywhere (A/B runs)
+    return big && env_on && ctx->ntt_kind != NTT_KIND_WAVE_W12_1024;
+}
+
+// A context-owned table of the first n powers of w^(2^sqr), w = the field's root of unity of order 2^log_w, in packed (Montgomery)
+// form: built on the first use of `key` in `cache` (V: the map's pointee — a field's element or void)
+template <class F, class V>
+static int wave_root_powers(plonk_ctx* ctx, std::map<unsigned, V*>& cache, unsigned key, unsigned log_w, bool inverse, unsigned sqr, size_t n,
+                            const Fp<typename F::P>** out) {
+    typedef Fp<typename F::P> E;
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        E w = F::root_of_unity(log_w, inverse);
+        for (unsigned i = 0; i < sqr; i++) w = fp_sqr(w);
+        void* d;
+        PLONK_TRY(ctx_table_alloc(ctx, n * sizeof(E), n, &d));
+        PLONK_TRY(F::powers(ctx, w, fp_one<typename F::P>(), (E*)d, n));
+        it = cache.emplace(key, (V*)d).first;
+    }
+    *out = (const E*)it->second;
+    return PLONK_OK;
+}
+// the two-level inter-pass twiddles w_N^e = lo[e & 1023] * hi[e >> 10]: entries of either table, and the packed pair
+static inline size_t ntt_lo_entries(unsigned log_n) { return (size_t)1 << (log_n < NTT_TW_LO_LOG ? log_n : NTT_TW_LO_LOG); }
+static inline size_t ntt_hi_entries(unsigned log_n) { return log_n > NTT_TW_LO_LOG ? (size_t)1 << (log_n - NTT_TW_LO_LOG) : 1; }
+template <class F, class V>
+static int wave_packed_lo_hi(plonk_ctx* ctx, std::map<unsigned, V*>& lo_cache, std::map<unsigned, V*>& hi_cache, unsigned log_n, bool inverse,
+                             const Fp<typename F::P>** lo, const Fp<typename F::P>** hi) {
+    const unsigned key = ntt_key(log_n, inverse);
+    PLONK_TRY((wave_root_powers<F, V>(ctx, lo_cache, key, log_n, inverse, 0, ntt_lo_entries(log_n), lo)));
+    return wave_root_powers<F, V>(ctx, hi_cache, key, log_n, inverse, NTT_TW_LO_LOG, ntt_hi_entries(log_n), hi);
+}
+
 template <class P> static int wave_limb_table(plonk_ctx* ctx, std::map<unsigned, int32_t*>& cache, unsigned key, const Fp<P>* packed, size_t n,
                                               const int32_t** out) {
     auto it = cache.find(key);
     if (it == cache.end()) {
-        void* d = nullptr;
+        void* d;
         Ninv261 ninv;
         fpl_ninv261<P>(ninv.l);
-        if (!plonk_dev_malloc(&d, n * NTT_SHOUP_STRIDE * sizeof(int32_t))) {
-            plonk_set_error("hipMalloc of a %zu-entry twiddle table failed", n);
-            return PLONK_ERR_NOMEM;
-        }
-        ctx->owned.push_back(d);
+        PLONK_TRY(ctx_table_alloc(ctx, n * NTT_SHOUP_STRIDE * sizeof(int32_t), n, &d));
         PLONK_LAUNCH(ntt_limb_table_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, packed, (int32_t*)d, n, ninv);
         PLONK_CHECK_HIP(hipGetLastError());
         it = cache.emplace(key, (int32_t*)d).first;
@@ -41,19 +114,15 @@ template <class P> static int wave_limb_table(plonk_ctx* ctx, std::map<unsigned,
 template <class F> static int wave_program_table(plonk_ctx* ctx, unsigned log_n, unsigned log_e, bool inverse, const int32_t** out) {
     typedef typename F::P P;
     WaveTables& T = F::tables(ctx);
-    const unsigned key = log_n | (inverse ? 256u : 0u) | (log_e << 12);  // (2^9 exists with eight and with two elements per thread)
+    const unsigned key = ntt_key(log_n, inverse, 0, 0, log_e);  // (2^9 exists with eight and with two elements per thread)
     auto it = T.prog.find(key);
     if (it == T.prog.end()) {
         const Fp<P>* packed;
         PLONK_TRY(F::packed_roots(ctx, log_n, inverse, &packed));
         const unsigned nlds = wavel_nlds(log_n, log_e), stages = wavel_tw_stages(log_e, nlds);
         const size_t entries = wavel_tw_offset(log_e, nlds, stages);
-        void* d = nullptr;
-        if (!plonk_dev_malloc(&d, entries * NTT_SHOUP_STRIDE * sizeof(int32_t))) {
-            plonk_set_error("hipMalloc of a %zu-entry twiddle table failed", entries);
-            return PLONK_ERR_NOMEM;
-        }
-        ctx->owned.push_back(d);
+        void* d;
+        PLONK_TRY(ctx_table_alloc(ctx, entries * NTT_SHOUP_STRIDE * sizeof(int32_t), entries, &d));
         Ninv261 ninv;
         fpl_ninv261<P>(ninv.l);
         for (unsigned st = 0; st < stages; st++) {
@@ -76,26 +145,25 @@ template <class F> static int wave_lo_hi(plonk_ctx* ctx, unsigned log_n, bool in
     WaveTables& T = F::tables(ctx);
     const Fp<P>*plo, *phi;
     PLONK_TRY(F::packed_lo_hi(ctx, log_n, inverse, &plo, &phi));
-    const unsigned key = log_n | (inverse ? 256u : 0u);
-    const unsigned log_lo = log_n < NTT_TW_LO_LOG ? log_n : NTT_TW_LO_LOG;
-    const size_t nhi = log_n > NTT_TW_LO_LOG ? ((size_t)1 << (log_n - NTT_TW_LO_LOG)) : 1;
-    PLONK_TRY(wave_limb_table<P>(ctx, T.lo, key, plo, (size_t)1 << log_lo, lo));
+    const unsigned key = ntt_key(log_n, inverse), key_scaled = ntt_key(log_n, inverse, NTT_KEY_SCALED);
+    const size_t nhi = ntt_hi_entries(log_n);
+    PLONK_TRY(wave_limb_table<P>(ctx, T.lo, key, plo, ntt_lo_entries(log_n), lo));
     if (!scaled) return wave_limb_table<P>(ctx, T.hi, key, phi, nhi, hi);
-    if (T.hi.find(key | 512u) == T.hi.end()) {  // (1/N) * w_hi^k, built once
+    if (T.hi.find(key_scaled) == T.hi.end()) {  // (1/N) * w_hi^k, built once
         Fp<P> whi = F::root_of_unity(log_n, inverse);
         for (unsigned i = 0; i < NTT_TW_LO_LOG; i++) whi = fp_sqr(whi);
-        void* tmp = nullptr;  // (not a scratch slot: callers hold those across this call)
+        void* tmp = nullptr;  // (not a scratch slot: callers hold those across this call; freed below, so not a context-owned table)
         if (!plonk_dev_malloc(&tmp, nhi * sizeof(Fp<P>))) {
             plonk_set_error("hipMalloc of a %zu-entry twiddle table failed", nhi);
             return PLONK_ERR_NOMEM;
         }
-        int rc = F::powers(ctx, whi, fp_inv(F::from_u64((uint64_t)1 << log_n)), (Fp<P>*)tmp, nhi);
-        if (rc == PLONK_OK) rc = wave_limb_table<P>(ctx, T.hi, key | 512u, (const Fp<P>*)tmp, nhi, hi);
+        int rc = F::powers(ctx, whi, host_fp_inv_pow2<P>(log_n), (Fp<P>*)tmp, nhi);
+        if (rc == PLONK_OK) rc = wave_limb_table<P>(ctx, T.hi, key_scaled, (const Fp<P>*)tmp, nhi, hi);
         hipStreamSynchronize(ctx->stream);  // the packed copy must outlive the conversion kernel only
         hipFree(tmp);
         return rc;
     }
-    return wave_limb_table<P>(ctx, T.hi, key | 512u, (const Fp<P>*)nullptr, nhi, hi);
+    return wave_limb_table<P>(ctx, T.hi, key_scaled, (const Fp<P>*)nullptr, nhi, hi);
 }
 
 // the column pass's inter-pass twiddles as one table in usage order (ntt_interpass_table_kernel), when the context's
@@ -106,23 +174,19 @@ static int wave_interpass_table(plonk_ctx* ctx, unsigned log_n, unsigned log_r1,
     WaveTables& T = F::tables(ctx);
     *out = nullptr;
     if (!ctx->ntt_table_budget || log_e1 == 3) return PLONK_OK;  // switched off (tables built earlier stay allocated, unused); not for the E = 8 column kernels
-    const unsigned key = log_n | (inverse ? 256u : 0u) | (scaled ? 512u : 0u) | (log_r1 << 12) | (log_e1 << 20);
+    const unsigned key = ntt_key(log_n, inverse, scaled ? NTT_KEY_SCALED : 0u, log_r1, log_e1);
     auto it = T.interpass.find(key);
     if (it == T.interpass.end()) {
         const size_t bytes = ((size_t)NTT_SHOUP_STRIDE * sizeof(int32_t)) << log_n;
         if (ctx->ntt_tables_bytes + bytes > ctx->ntt_table_budget) return PLONK_OK;
         const Fp<P>*plo, *phi;
         PLONK_TRY(F::packed_lo_hi(ctx, log_n, inverse, &plo, &phi));
-        void* d = nullptr;
-        if (!plonk_dev_malloc(&d, bytes)) {
-            (void)hipGetLastError();  // not an error of the transform: the two small tables serve it
-            return PLONK_OK;
-        }
-        ctx->owned.push_back(d);
+        void* d;
+        if (ctx_table_alloc(ctx, bytes, 0, &d) != PLONK_OK) return PLONK_OK;  // not an error of the transform (no message): the two small tables serve it
         ctx->ntt_tables_bytes += bytes;
         Ninv261 ninv;
         fpl_ninv261<P>(ninv.l);
-        const Fp<P> scale = scaled ? fp_inv(F::from_u64((uint64_t)1 << log_n)) : fp_one<P>();
+        const Fp<P> scale = scaled ? host_fp_inv_pow2<P>(log_n) : fp_one<P>();
         PLONK_LAUNCH(ntt_interpass_table_kernel<P>, dim3((unsigned)((((size_t)1 << log_n) + 255) / 256)), dim3(256), 0, ctx->stream, plo, phi, scale, log_n,
                      log_r1, log_e1, (int32_t*)d, ninv);
         PLONK_CHECK_HIP(hipGetLastError());
@@ -138,12 +202,11 @@ template <class F> static int wave_jm(plonk_ctx* ctx, const int32_t** out) {
     if (!T.jm) {
         int32_t host[(2 * FPL_RS_J + 1) * 12];
         for (int j = -FPL_RS_J; j <= FPL_RS_J; j++) fpl_jm_entry<typename F::P>(j, host + (j + FPL_RS_J) * 12);
-        void* d = nullptr;
-        if (!plonk_dev_malloc(&d, sizeof host)) {
+        void* d;
+        if (ctx_table_alloc(ctx, sizeof host, 0, &d) != PLONK_OK) {
             plonk_set_error("hipMalloc of the NTT range-reduction table failed");
             return PLONK_ERR_NOMEM;
         }
-        ctx->owned.push_back(d);
         PLONK_CHECK_HIP(hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice));
         T.jm = (const int32_t*)d;
     }
@@ -218,20 +281,9 @@ template <class F> static int wave_launch(plonk_ctx* ctx, const NttWaveT<typenam
 // call of a (size, direction, scaling, table choice) and cached per context and field: the host-side field arithmetic —
 // a root of unity by repeated squaring, a 261-bit Hensel lift, a modular inversion, ~20 us in all — used to run on EVERY
 // call, and a lone 2^16 transform is ~10 us of device time (0.031 ms measured).
-// PLONK_NTT_W12 = 4: keep 2^12 on the 1024-thread 4-element kernel everywhere (A/B runs)
-static inline bool wave_w12_as_512x8() {
-    static const bool on = [] {
-        const char* e = getenv("PLONK_NTT_W12");
-        return !(e && atoi(e) == 4);
-    }();
-    return on;
-}
-
+// PLONK_NTT_TMP_TRANSPOSED = 0: the intermediate buffer as [k1][c] (A/B runs; wave_plan_get)
 static inline bool wave_tmp_transposed() {
-    static const bool on = [] {
-        const char* e = getenv("PLONK_NTT_TMP_TRANSPOSED");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = wave_env_int("PLONK_NTT_TMP_TRANSPOSED", 1) != 0;
     return on;
 }
 
@@ -241,10 +293,8 @@ template <class P> struct WavePlan {
     NttWaveT<P> a, c;  // single pass: a;  two passes: a = columns, c = rows
 };
 
-// big: the call has at least 2^20 elements (the 512-thread form of 2^12 pays from there: profiles/r04_f_ntt_2e12_forms_ab.jsonl)
 template <class F>
-static int wave_plan_get(plonk_ctx* ctx, unsigned log_n, bool inverse, bool scale_by_n_inv, bool want_full, bool latency, bool big,
-                         const WavePlan<typename F::P>** out) {
+static int wave_plan_get(plonk_ctx* ctx, unsigned log_n, bool inverse, bool scale_by_n_inv, unsigned form, const WavePlan<typename F::P>** out) {
     typedef typename F::P P;
     typedef Fp<P> E;
     WaveTables& T = F::tables(ctx);
@@ -252,7 +302,8 @@ static int wave_plan_get(plonk_ctx* ctx, unsigned log_n, bool inverse, bool scal
         T.plans.clear();
         T.plan_epoch = ctx->ntt_cfg_epoch;
     }
-    const unsigned key = log_n | (inverse ? 256u : 0u) | (scale_by_n_inv ? 512u : 0u) | (want_full ? 1024u : 0u) | (latency ? 2048u : 0u) | (big ? 4096u : 0u);
+    const bool latency = form & NTT_KEY_LATENCY;
+    const unsigned key = ntt_key(log_n, inverse, form | (scale_by_n_inv ? NTT_KEY_SCALED : 0u));
     auto it = T.plans.find(key);
     if (it != T.plans.end()) {
         *out = static_cast<const WavePlan<P>*>(it->second.get());
@@ -264,28 +315,22 @@ static int wave_plan_get(plonk_ctx* ctx, unsigned log_n, bool inverse, bool scal
     PLONK_REQUIRE(ntt_wave_plan(ctx, log_n, latency, &log_r1, &log_r2), PLONK_ERR_ARG, "no wave-kernel plan for 2^%u points", log_n);
     plan->log_r1 = log_r1;
     plan->log_r2 = log_r2;
-    // 2^12 runs as 512 threads x 8 elements (two workgroups per CU) as a single pass and as a row pass of calls with at least 2^20
-    // elements: 18.0 -> 19.2 G elements/s at 512 transforms, 17.7 -> 20.7 at 4096, row passes +2 .. 5 %; a small call is faster on
-    // the 1024-thread kernel's shorter chain (a lone 2^12: 0.043 against 0.048 ms).  A column pass stays on the 1024-thread
-    // 4-element kernel (the one-table inter-pass twiddles need its register room; ntt_wave.h)
-    const bool w12 = big && wave_w12_as_512x8() && ctx->ntt_kind != 8;  // (kind 8: 2^12 on the 1024-thread form everywhere — tests, A/B)
+    const bool w12 = ntt_policy_w12_as_512x8(ctx, form & NTT_KEY_BIG);
     const unsigned log_e1 = plan->log_e1 = (log_r1 == 12 && w12 && !log_r2) ? 3u : wavel_log_e(log_r1, latency);
     const unsigned log_e2 = plan->log_e2 = !log_r2 ? 0u : ((log_r2 == 12 && w12) ? 3u : wavel_log_e(log_r2, latency));
     NttWaveT<P> p;
     wave_params_init<F>(&p, log_n, inverse);
     PLONK_TRY(wave_jm<F>(ctx, &p.jm));
     E n_inv = fp_zero<P>();
-    if (scale_by_n_inv) n_inv = fp_inv(F::from_u64((uint64_t)N));
+    if (scale_by_n_inv) n_inv = host_fp_inv_pow2<P>(log_n);
     if (!log_r2) {
         PLONK_TRY(wave_program_table<F>(ctx, log_n, log_e1, inverse, &p.roots));
         p.out_scalar = n_inv;
         p.has_out_scalar = scale_by_n_inv;
         plan->a = p;
     } else {
-        // (measured, profiles/r03_m_ntt_sweep.jsonl: the table wins 4-10 % wherever the column pass fills the chip; a lone 2^18 —
-        // one workgroup per CU, every load latency exposed — is 5 % faster on the small, L2-resident tables)
         const int32_t* full = nullptr;
-        if (want_full) PLONK_TRY(wave_interpass_table<F>(ctx, log_n, log_r1, log_e1, inverse, scale_by_n_inv, &full));
+        if (form & NTT_KEY_FULL) PLONK_TRY(wave_interpass_table<F>(ctx, log_n, log_r1, log_e1, inverse, scale_by_n_inv, &full));
         if (full) {
             p.tw_lo = full;
             p.tw_always = 2u;
@@ -331,39 +376,35 @@ static inline bool wave_fan_ok(const NttFan& f, size_t N, bool has_out_scale) {
 }
 
 // one transform per batch entry: a single launch for 2^8 .. 2^13, columns then rows through scratch slot 0 for 2^14 .. 2^26
-template <class F>
-static int wave_run(plonk_ctx* ctx, const Fp<typename F::P>* in, Fp<typename F::P>* out, unsigned log_n, bool inverse, size_t batch, size_t in_len,
-                    size_t in_bstride, size_t out_bstride, const Fp<typename F::P>* in_scale, const Fp<typename F::P>* out_scale, bool scale_by_n_inv,
-                    const NttFan* fan = nullptr) {
+template <class F> static int wave_run(plonk_ctx* ctx, const NttCallT<Fp<typename F::P>>& call) {
     typedef typename F::P P;
     typedef Fp<P> E;
-    const size_t N = (size_t)1 << log_n;
-    PLONK_REQUIRE(!fan || (log_n <= 13 && wave_fan_ok(*fan, N, out_scale != nullptr)), PLONK_ERR_ARG,
+    const NttCallT<E> t = ntt_call_resolved(call);
+    const unsigned log_n = t.log_n;
+    const size_t N = (size_t)1 << log_n, batch = t.batch;
+    const bool fan = t.fan.count > 1;
+    PLONK_REQUIRE(!fan || (log_n <= 13 && wave_fan_ok(t.fan, N, t.out_scale != nullptr)), PLONK_ERR_ARG,
                   "a fanned transform needs a single-pass size (2^7 .. 2^13) and strides of 0 or N");
-    const bool want_full = log_n >= 14 && (log_n <= 16 || ((size_t)batch << log_n) >= ((size_t)1 << 19));
-    // a small job waits for one wave's instruction chain: the two-element forms (plonk_ntt_select_kernel 6 / 7: never / always — tests, A/B runs)
-    const bool latency = ctx->ntt_kind == 6 ? false : (ctx->ntt_kind == 7 || ((size_t)batch << log_n) <= ((size_t)1 << 18));
     const WavePlan<P>* plan;
-    const bool big = ctx->ntt_kind == 6 || ((size_t)batch << log_n) >= ((size_t)1 << 20);
-    PLONK_TRY(wave_plan_get<F>(ctx, log_n, inverse, scale_by_n_inv, want_full, latency, big, &plan));
+    PLONK_TRY(wave_plan_get<F>(ctx, log_n, t.inverse, t.scale_by_n_inv, ntt_policy_form(ctx, log_n, batch), &plan));
     const unsigned log_r1 = plan->log_r1, log_r2 = plan->log_r2;
-    const unsigned in_len32 = (unsigned)(in_len < N ? in_len : N);
+    const unsigned in_len32 = (unsigned)(t.in_len < N ? t.in_len : N);
     if (!log_r2) {
         NttWaveT<P> p = plan->a;
-        p.in_bstride = in_bstride;
-        p.out_bstride = out_bstride;
+        p.in_bstride = t.in_bstride;
+        p.out_bstride = t.out_bstride;
         p.in_len = in_len32;
-        p.in_scale = in_scale;
-        p.out_scale = out_scale;
-        if (fan) p.fan = (fan->in_stride ? NTT_FAN_IN : 0u) | (fan->out_stride ? NTT_FAN_OUT : 0u) | (fan->scale_stride ? NTT_FAN_SCALE : 0u);
+        p.in_scale = t.in_scale;
+        p.out_scale = t.out_scale;
+        if (fan) p.fan = (t.fan.in_stride ? NTT_FAN_IN : 0u) | (t.fan.out_stride ? NTT_FAN_OUT : 0u) | (t.fan.scale_stride ? NTT_FAN_SCALE : 0u);
         // an in-place transform is safe: every thread has read all of its inputs before any thread stores (the stages
         // in between are separated by barriers for L > 0; for L = 0 the single wave runs in lock step)
         PLONK_TRY(prof_begin(ctx, "ntt_pass", 64.0 * (double)N * (double)batch));
         for (size_t b0 = 0; b0 < batch; b0 += (size_t)1 << 30) {  // grid.x carries the batch
             const size_t nb = batch - b0 < ((size_t)1 << 30) ? batch - b0 : (size_t)1 << 30;
-            p.in = in + b0 * in_bstride;
-            p.out = out + b0 * out_bstride;
-            PLONK_TRY(wave_launch<F>(ctx, p, log_n, plan->log_e1, (unsigned)nb, fan ? fan->count : 1));
+            p.in = t.in + b0 * t.in_bstride;
+            p.out = t.out + b0 * t.out_bstride;
+            PLONK_TRY(wave_launch<F>(ctx, p, log_n, plan->log_e1, (unsigned)nb, fan ? t.fan.count : 1));
         }
         PLONK_TRY(prof_end(ctx));
         PLONK_CHECK_HIP(hipGetLastError());  // a refused launch (thread-local, no synchronisation)
@@ -376,15 +417,15 @@ static int wave_run(plonk_ctx* ctx, const Fp<typename F::P>* in, Fp<typename F::
     E* tmp = (E*)sc;
     NttWaveT<P> c = plan->c;
     c.in = tmp;
-    c.out = out;
-    c.out_bstride = out_bstride;
-    c.out_scale = out_scale;
+    c.out = t.out;
+    c.out_bstride = t.out_bstride;
+    c.out_scale = t.out_scale;
     NttWaveT<P> a = plan->a;
-    a.in = in;
+    a.in = t.in;
     a.out = tmp;
-    a.in_bstride = in_bstride;
+    a.in_bstride = t.in_bstride;
     a.in_len = in_len32;
-    a.in_scale = in_scale;
+    a.in_scale = t.in_scale;
     PLONK_TRY(prof_begin(ctx, "ntt_pass_columns", 32.0 * (double)N * (double)batch));
     PLONK_TRY(wave_launch<F>(ctx, a, log_r1, plan->log_e1, 1u << log_r2, (unsigned)batch));
     PLONK_TRY(prof_end(ctx));

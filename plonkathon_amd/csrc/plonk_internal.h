@@ -66,12 +66,15 @@ static inline int dev_grow(hipStream_t stream, size_t* cap, size_t need, std::in
     return PLONK_OK;
 }
 
-static inline Fr host_fr_u64(uint64_t x) {  // a small integer in Montgomery form
-    Fr a = fp_zero<FrParams>();
+// a small integer in Montgomery form, and 1 / 2^log_n (the inverse transform's factor): the host-side routines of every field
+template <class P> static inline Fp<P> host_fp_u64(uint64_t x) {
+    Fp<P> a = fp_zero<P>();
     a.v[0] = (uint32_t)x;
     a.v[1] = (uint32_t)(x >> 32);
     return fp_to_mont(a);
 }
+template <class P> static inline Fp<P> host_fp_inv_pow2(unsigned log_n) { return fp_inv(host_fp_u64<P>((uint64_t)1 << log_n)); }
+static inline Fr host_fr_u64(uint64_t x) { return host_fp_u64<FrParams>(x); }
 
 #define PLONK_REQUIRE(cond, code, ...)    \
     do {                                  \
@@ -96,19 +99,27 @@ int plonk_use_device(int device);
         if (rc_ != PLONK_OK) return rc_; \
     } while (0)
 
-// device tables of the wave NTT kernels for one field, cached per context (the memory is in plonk_ctx::owned)
+// Key of an entry in the transform engine's per-context caches (tables and launch plans): a cache names the fields its entries depend on,
+// distinct fields give distinct keys.  SCALED: the table (or the plan's output) carries the inverse's 1/N; FULL, LATENCY, BIG: a plan's form (ntt_policy_form)
+enum : unsigned { NTT_KEY_SCALED = 1, NTT_KEY_FULL = 2, NTT_KEY_LATENCY = 4, NTT_KEY_BIG = 8 };
+static inline unsigned ntt_key(unsigned log_n, bool inverse, unsigned flags = 0, unsigned log_r1 = 0, unsigned log_e = 0) {
+    return log_n | (inverse ? 64u : 0u) | (flags << 8) | (log_r1 << 16) | (log_e << 24);  // log_n <= 32, log_r1 <= 13, log_e <= 3
+}
+
+// device tables of the wave NTT kernels for one field, cached per context (the memory is in plonk_ctx::owned); keys: ntt_key
 struct WaveTables {
-    std::map<unsigned, int32_t*> prog, lo, hi;  // keys: log2(size) | inverse << 8 (| 512: hi scaled by 1/N)
-    std::map<unsigned, int32_t*> interpass;     // full inter-pass tables: log2 N | inverse << 8 | scaled << 9 | log2 R1 << 12
+    std::map<unsigned, int32_t*> prog;          // a kernel's twiddles in program order, per (size, direction, elements per thread as log_e)
+    std::map<unsigned, int32_t*> lo, hi;        // the two-level inter-pass twiddles, per (size, direction); hi also SCALED
+    std::map<unsigned, int32_t*> interpass;     // full inter-pass tables, per (size, direction, SCALED, log_r1, log_e of the column kernel)
     const int32_t* jm = nullptr;                // fpl_reduce_small's multiples of the modulus
     bool attr_set[4] = {false, false, false, false};   // hipFuncSetAttribute is per device: tracked per context (E = 4, E = 8, E = 4 column kernel, the 512-thread 2^12 kernel)
-    std::map<unsigned, void*> packed[3];        // packed source tables (full, lo, hi) of a field that has no cache of its own (BLS12-381 Fr)
-    std::map<unsigned, std::shared_ptr<void>> plans;  // WavePlan<P> per (log2 N | inverse << 8 | 1/N << 9 | full table << 10): ntt_wave_host.h
+    std::map<unsigned, void*> packed[3];        // packed source tables (full, lo, hi) of a field that has no cache of its own (BLS12-381 Fr), per (size, direction)
+    std::map<unsigned, std::shared_ptr<void>> plans;  // WavePlan<P> per (size, direction, SCALED, FULL, LATENCY, BIG): ntt_wave_host.h
     unsigned plan_epoch = 0;                    // plonk_ctx::ntt_cfg_epoch the plans were built under
 };
 
 struct NttTables {
-    // keys are log2(size) | inverse << 8
+    // per (size, direction)
     std::map<unsigned, Fr*> small;   // w_R^k, k < R/2              (per-pass LDS twiddles)
     std::map<unsigned, Fr*> lo, hi;  // w_N^e = lo[e & 1023] * hi[e >> 10]   (inter-pass twiddles)
     std::map<unsigned, Fr*> full;    // w_N^k, k < N                 (barycentric / permutation argument)
@@ -187,7 +198,7 @@ struct plonk_ctx {
     size_t ntt_table_budget = (size_t)4 << 30, ntt_tables_bytes = 0;  // full inter-pass twiddle tables (80 B per point and direction): plonk_ntt_set_table_budget
     unsigned char ntt_split[32] = {0};  // plonk_ntt_set_split: log2 R1 of the two-pass wave plan per log2 N (0 = default)
     unsigned ntt_cfg_epoch = 0;  // bumped by every plonk_ntt_* setter: cached launch plans are rebuilt
-    unsigned ntt_kind = 0;  // 0 = auto (wave kernels where they apply, else the LDS kernel), 1 / 4 = the LDS kernel, 5 = force wave, 6 / 7 = force wave without / with the two-element latency forms, 8 = force wave with 2^12 on 1024 threads
+    unsigned ntt_kind = 0;  // an NttKind (ntt_wave_host.h, with the policy it selects): plonk_ntt_select_kernel
 };
 
 // grid of a grid-stride kernel over n items
@@ -200,6 +211,8 @@ static inline dim3 grid1(size_t n, unsigned block = 256, size_t cap = 4096) {
 
 // scratch slot use: 0 = NTT inter-pass buffer, 1 = MSM digits/partials, 2-3 = API-level temporaries
 int ctx_scratch(plonk_ctx* ctx, int slot, size_t bytes, void** out);
+// a device table released with the context (plonk_ctx::owned); `entries` goes into the out-of-memory message (0: none — the caller has a fallback, or its own text)
+int ctx_table_alloc(plonk_ctx* ctx, size_t bytes, size_t entries, void** out);
 int ctx_copy_stream(plonk_ctx* ctx);
 // bracket an instrumented launch: prof_begin before, prof_end after (no-ops unless profiling)
 int prof_begin(plonk_ctx* ctx, const char* name, double algo_bytes);
@@ -233,8 +246,34 @@ Fr host_root_of_unity(unsigned log_n, bool inverse);
 // and takes its scaling vector at in_scale / out_scale + f scale_stride (elements): one launch on the wave kernels' single-pass
 // sizes (the prover: a coefficient vector evaluated on three cosets), a loop of calls elsewhere
 struct NttFan { unsigned count, in_stride, out_stride, scale_stride; };
-int ntt_run(plonk_ctx*, const Fr* in, Fr* out, unsigned log_n, bool inverse, size_t batch, size_t in_len,
-            size_t in_bstride, size_t out_bstride, const Fr* in_scale, const Fr* out_scale, bool scale_by_n_inv, const NttFan* fan = nullptr);
+// One call of the engine: `batch` transforms of 2^log_n points, entry b read at in + b in_bstride (its first in_len elements; the
+// rest count as zero) and written at out + b out_bstride.  in_scale / out_scale: vectors multiplied in at the first load / last
+// store; scale_by_n_inv: the output times 1/N.  A length or stride of 0 stands for N = 2^log_n (ntt_run and wave_run resolve it
+// first thing; no caller means a zero-length input, so nothing is misread).  E: the field's element (BLS12-381 Fr: ntt_bls.hip).
+template <class E> struct NttCallT {
+    const E* in; E* out; unsigned log_n; bool inverse;
+    size_t batch = 1;
+    size_t in_len = 0, in_bstride = 0, out_bstride = 0;  // 0 = N
+    const E* in_scale = nullptr; const E* out_scale = nullptr;
+    bool scale_by_n_inv = false;
+    NttFan fan = {};  // count <= 1: none
+};
+typedef NttCallT<Fr> NttCall;
+// the common shapes: `batch` contiguous vectors, forward, or inverse with its 1/N
+template <class E> static inline NttCallT<E> ntt_forward(const E* in, E* out, unsigned log_n, size_t batch) { return NttCallT<E>{in, out, log_n, false, batch}; }
+template <class E> static inline NttCallT<E> ntt_inverse(const E* in, E* out, unsigned log_n, size_t batch) {
+    NttCallT<E> t{in, out, log_n, true, batch};
+    t.scale_by_n_inv = true;
+    return t;
+}
+template <class E> static inline NttCallT<E> ntt_call_resolved(NttCallT<E> t) {
+    const size_t N = (size_t)1 << t.log_n;
+    if (!t.in_len) t.in_len = N;
+    if (!t.in_bstride) t.in_bstride = N;
+    if (!t.out_bstride) t.out_bstride = N;
+    return t;
+}
+int ntt_run(plonk_ctx*, const NttCall&);
 int ntt_get_roots(plonk_ctx*, unsigned log_n, bool inverse, const Fr** table_full);
 int ntt_dist_plan(unsigned log_n, unsigned log_w, unsigned* log_r1, unsigned* log_r2);
 bool ntt_wave_plan(const plonk_ctx* ctx /* null: the default splits */, unsigned log_n, bool latency, unsigned* log_r1, unsigned* log_r2);

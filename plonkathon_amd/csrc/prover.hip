@@ -515,6 +515,16 @@ int plonk_prover_create_multi(plonk_ctx* ctx, plonk_srs* srs, unsigned log_n, si
 
 }  // extern "C"
 
+// `batch` coefficient vectors onto the cosets g mu^r H: P(g mu^r w^j) is the size-n transform of c_i (g mu^r)^i — one input, qcosets
+// scalings, outputs [r][n] side by side
+static NttCall coset_call(const plonk_prover::Circuit& c, const Fr* in, Fr* out, size_t batch) {
+    NttCall t = ntt_forward(in, out, c.log_n, batch);
+    t.out_bstride = c.qcosets * c.n;
+    t.in_scale = c.g_pow;
+    t.fan = NttFan{c.qcosets, 0u, (unsigned)c.n, (unsigned)c.n};
+    return t;
+}
+
 // Everything of the circuit that lives on the cosets g mu^r H, r < qcosets, anew: plonk_prover_create for three, and
 // plonk_prover_set_options when PLONK_PROVER_BLINDING changes their number.
 static void free_coset_tables(plonk_prover::Circuit& c) {
@@ -540,15 +550,13 @@ static int coset_tables(plonk_prover* p) {
         PLONK_TRY(k_fr_powers(ctx, c.w, base, c.x_big + r * n, n));
         base = fp_mul(base, mu);
     }
-    // the circuit polynomials' values on the cosets: P(g mu^r w^j) is the size-n transform of c_i (g mu^r)^i
-    const NttFan fan{c.qcosets, 0u, (unsigned)n, (unsigned)n};
-    PLONK_TRY(ntt_run(ctx, c.fixed_coef, c.fixed_big, log_n, false, 8 * K, n, n, n3, c.g_pow, nullptr, false, &fan));  // [K][8][qcosets][n]
+    PLONK_TRY(ntt_run(ctx, coset_call(c, c.fixed_coef, c.fixed_big, 8 * K)));  // the circuit polynomials' values on the cosets: [K][8][qcosets][n]
     // L0: Lagrange vector e_0 has coefficient form (1/n, 1/n, ...)          prover.py:184-186
     void* tmpv;
     PLONK_TRY(ctx_scratch(ctx, 2, n * e, &tmpv));  // context-owned scratch: nothing to leak on an error path
     Fr* tmp = (Fr*)tmpv;
     PLONK_TRY(k_fr_powers(ctx, one, c.n_inv, tmp, n));
-    PLONK_TRY(ntt_run(ctx, tmp, c.l0_big, log_n, false, 1, n, n, n3, c.g_pow, nullptr, false, &fan));
+    PLONK_TRY(ntt_run(ctx, coset_call(c, tmp, c.l0_big, 1)));
     if (c.sparse_pi && c.n_public) {
         Zh4 zh4;
         for (int k = 0; k < 4; k++) zh4.v[k] = c.zh[k];
@@ -609,7 +617,7 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
     c.chal = challenge_consts();
     c.g = host_fr_u64(5);  // multiplicative generator (curve.py:5): g^(4n) != 1, so Z_H != 0 on the coset
     c.w = host_root_of_unity(log_n, false);
-    c.n_inv = fp_inv(host_fr_u64((uint64_t)n));
+    c.n_inv = host_fp_inv_pow2<FrParams>(log_n);
     c.half = fp_inv(host_fr_u64(2));
     const size_t e = sizeof(Fr);
     PLONK_TRY(dev_alloc((void**)&c.fixed_lag, K * 8 * n * e));
@@ -618,7 +626,7 @@ static int prover_init(plonk_prover* p, plonk_ctx* ctx, plonk_srs* srs, unsigned
     PLONK_TRY(intake_init(p, selectors_le32));
     PLONK_TRY(ntt_get_roots(ctx, log_n, false, &c.roots));
     // coefficient forms of the 8 circuit polynomials
-    PLONK_TRY(ntt_run(ctx, c.fixed_lag, c.fixed_coef, log_n, true, 8 * K, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(ntt_run(ctx, ntt_inverse(c.fixed_lag, c.fixed_coef, log_n, 8 * K)));
     // Z_H on coset r is the constant (g mu^r)^n - 1 = g^n i^r - 1, i = mu^n            prover.py:178
     const Fr one = fp_one<FrParams>();
     Fr gn = c.g;
@@ -704,11 +712,11 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_LAUNCH(gate_check_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)r.wit_lag, pub, c.n_public,
                  c.sparse_pi ? (const Fr*)nullptr : (const Fr*)(r.wit_lag + 3 * B * n), (const Fr*)c.fixed_lag, cid, n, B, r.closes + B);  // prover.py:108-116
     if (c.sparse_pi) {
-        PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 3 * B, n, n, n, nullptr, nullptr, true));
+        PLONK_TRY(ntt_run(ctx, ntt_inverse(r.wit_lag, r.coef, log_n, 3 * B)));
         if (c.n_public) PLONK_LAUNCH(pi_coeffs_kernel, grid1(B * n), dim3(256), 0, s, pub, c.n_public, c.roots_inv, n, B, c.n_inv, r.coef + 3 * B * n);
         else PLONK_CHECK_HIP(hipMemsetAsync(r.coef + 3 * B * n, 0, B * n * sizeof(Fr), s));
     } else {
-        PLONK_TRY(ntt_run(ctx, r.wit_lag, r.coef, log_n, true, 4 * B, n, n, n, nullptr, nullptr, true));
+        PLONK_TRY(ntt_run(ctx, ntt_inverse(r.wit_lag, r.coef, log_n, 4 * B)));
     }
     PLONK_TRY(commit(p, B, r.wit_lag, r.coef, 3, 0));
     if (blind) blind_commit(p, B, 0, 3);
@@ -725,7 +733,7 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     PLONK_TRY(prof_begin(ctx, "prover_grand_product", 11.0 * 32.0 * (double)n * (double)B));
     PLONK_TRY(scan_grand_product(s, S, gp, c.roots, state, RoundChallenges{}, n, B, r.z_lag, r.closes, r.num, r.wz, r.seg));  // num / wz: scratch until round 5
     PLONK_TRY(prof_end(ctx));
-    PLONK_TRY(ntt_run(ctx, r.z_lag, r.coef + 4 * B * n, log_n, true, B, n, n, n, nullptr, nullptr, true));
+    PLONK_TRY(ntt_run(ctx, ntt_inverse(r.z_lag, r.coef + 4 * B * n, log_n, B)));
     PLONK_TRY(commit(p, B, r.z_lag, r.coef + 4 * B * n, 1, 3));
     if (blind) blind_commit(p, B, 3, 1);
     transcript_round(p, B, 2);
@@ -736,14 +744,13 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     // Blinded, deg t = 3n + 5: the same on all four cosets (n3 = 4n), the tails' values added to the coset forms in between, and
     // blind_combine_kernel in quotient_combine_kernel's place.
     const size_t n3 = c.qcosets * n;
-    const NttFan fan{c.qcosets, 0u, (unsigned)n, (unsigned)n};  // one input, three scalings (g mu^r)^i, outputs [r][n] side by side
     if (c.sparse_pi) {  // A, B, C and Z through the transform, PI from the Lagrange basis on the coset
-        PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 3 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
-        PLONK_TRY(ntt_run(ctx, r.coef + 4 * B * n, r.big + 4 * B * n3, log_n, false, B, n, n, n3, c.g_pow, nullptr, false, &fan));
+        PLONK_TRY(ntt_run(ctx, coset_call(c, r.coef, r.big, 3 * B)));
+        PLONK_TRY(ntt_run(ctx, coset_call(c, r.coef + 4 * B * n, r.big + 4 * B * n3, B)));
         if (c.n_public) PLONK_LAUNCH(pi_coset_kernel, grid1(B * n3), dim3(256), 0, s, pub, c.n_public, (const Fr*)c.li_big, n3, B, r.big + 3 * B * n3);
         else PLONK_CHECK_HIP(hipMemsetAsync(r.big + 3 * B * n3, 0, B * n3 * sizeof(Fr), s));
     } else {
-        PLONK_TRY(ntt_run(ctx, r.coef, r.big, log_n, false, 5 * B, n, n, n3, c.g_pow, nullptr, false, &fan));
+        PLONK_TRY(ntt_run(ctx, coset_call(c, r.coef, r.big, 5 * B)));
     }
     if (blind) {
         BlindZh bz;
@@ -761,8 +768,11 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
     qi.fixed_stride = (unsigned)(FX_COUNT * n3);
     PLONK_LAUNCH(quotient_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)B), dim3(256), 0, s, qi, zh, (const ProofState*)state, RoundChallenges{},
                  (unsigned)n3, r.quot, log_n, (unsigned)n4);
-    const NttFan slices{c.qcosets, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
-    PLONK_TRY(ntt_run(ctx, r.quot, r.quot, log_n, true, B, n, n4, n4, nullptr, c.ginv_pow, false, &slices));
+    NttCall back{r.quot, r.quot, log_n, true, B};  // (1/n rides in ginv_pow)
+    back.in_bstride = back.out_bstride = n4;
+    back.out_scale = c.ginv_pow;
+    back.fan = NttFan{c.qcosets, (unsigned)n, (unsigned)n, (unsigned)n};  // the three coset slices of every quotient row, in place
+    PLONK_TRY(ntt_run(ctx, back));
     if (blind) {
         const BlindCombine bc = {c.comb_i, c.half, fp_mul(c.comb_g1, c.half), c.comb_g2, fp_mul(c.comb_g2, c.comb_g1)};
         PLONK_LAUNCH(blind_combine_kernel, grid1(B * n), dim3(256), 0, s, r.quot, n, n4, B, bc, bs);

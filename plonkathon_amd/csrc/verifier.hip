@@ -602,7 +602,7 @@ static int verifier_init(plonk_verifier* v, plonk_ctx* ctx, unsigned K, const un
             t.n_public = (uint32_t)n_public[c];
             t.w = host_root_of_unity(log_n[c], false);
             t.w_inv = host_root_of_unity(log_n[c], true);
-            t.n_inv = fp_inv(host_fr_u64((uint64_t)1 << log_n[c]));
+            t.n_inv = host_fp_inv_pow2<FrParams>(log_n[c]);
             for (int k = 0; k < 8; k++) {
                 const uint8_t* q = vk_xy_le + 64 * (8 * (size_t)c + k);
                 G1Affine& base = bases[8 * (size_t)c + k];
