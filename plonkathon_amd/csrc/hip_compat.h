@@ -67,13 +67,16 @@
 // PLONK_BESIDE_ACC(lanes, bit): the launch bounds of a short kernel that has a SMALL FORM — compiled for five waves per SIMD, at most
 // 96 VGPRs, what is free on a SIMD beside four waves of msm_comb_rows_kernel (104 each of 512), so that its workgroups need not wait
 // for a whole accumulation workgroup to retire.  A kernel takes the small form where bit `bit` of PLONK_SMALL_FORMS is set: 1
-// msm_comb_finalize_kernel, 2 msm_comb_rowsum_kernel, 4 grand_product_kernel, 16 linearisation_weights_kernel.  (eval_kernel has no such
-// form: its 56 KB of LDS hold a SIMD to two waves, the compiler drops a request for five, and a direct cap — amdgpu_num_vgpr(96) —
-// gave 192 registers and 216 bytes of scratch.)  Each was
-// decided by measurement (profiles/short_kernel_priority.txt: registers, scratch and durations of both forms); the default is the
-// set that was kept: all four.  (A/B builds: make EXTRA=-DPLONK_SMALL_FORMS=0.)
+// msm_comb_finalize_kernel, 2 msm_comb_rowsum_kernel, 4 grand_product_kernel, 8 eval_kernel and eval_seg_kernel, 16
+// linearisation_weights_kernel, 32 msm_comb_slow_kernel, 64 quotient_kernel.  The bit switches launch bounds only.  eval_kernel's
+// small form exists since the evaluations walk their rows in passes and add up inside the waves (prover_scans.h: 92 VGPRs, no
+// scratch, 896 bytes of LDS, where seven chains at once and a tree over 56 KB of LDS held a SIMD to two waves whatever was asked);
+// msm_comb_slow_kernel's since its rare branch is inline (the out-of-line helper alone held 97 registers).  Each was decided by
+// measurement — a form is kept if its in-step mean falls by more than its lone mean grows (profiles/short_kernel_priority.txt,
+// profiles/serial_path_small_forms.txt: registers, scratch and durations of both forms); the default is the set that was kept: all
+// seven.  (A/B builds: make EXTRA=-DPLONK_SMALL_FORMS=0.)
 #ifndef PLONK_SMALL_FORMS
-#define PLONK_SMALL_FORMS 23
+#define PLONK_SMALL_FORMS 127
 #endif
 #define PLONK_BESIDE_ACC(lanes, bit) PLONK_BESIDE_ACC_##bit(lanes)
 #if (PLONK_SMALL_FORMS) & 1
@@ -95,6 +98,21 @@
 #define PLONK_BESIDE_ACC_16(lanes) __launch_bounds__(lanes, 5)
 #else
 #define PLONK_BESIDE_ACC_16(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 8
+#define PLONK_BESIDE_ACC_8(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_8(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 32
+#define PLONK_BESIDE_ACC_32(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_32(lanes) __launch_bounds__(lanes)
+#endif
+#if (PLONK_SMALL_FORMS) & 64
+#define PLONK_BESIDE_ACC_64(lanes) __launch_bounds__(lanes, 5)
+#else
+#define PLONK_BESIDE_ACC_64(lanes) __launch_bounds__(lanes)
 #endif
 
 // PLONK_CHAIN(acc): an empty statement that merely USES the running 64-bit column sum of a product-scanning

@@ -698,7 +698,7 @@ template <unsigned LPM> __global__ void PLONK_BESIDE_ACC(64, 1) msm_comb_finaliz
 // list — the normal case — every workgroup reads the counter and returns.  Lane t: Horner over the columns of the scalars t, t + 256, ..
 // (rs, is): the digits' row and item strides (msm_comb_digits_kernel).  M bounds the list (the counter cannot pass it: an MSM is
 // appended once).
-__global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits, size_t n, size_t rs,
+__global__ void PLONK_BESIDE_ACC(256, 32) msm_comb_slow_kernel(const G1Affine* lookup, unsigned hb, unsigned a, const uint32_t* digits, size_t n, size_t rs,
                                                             size_t is, const uint32_t* redo, unsigned M, Fq* out_xy, uint8_t* flags, unsigned n_real,
                                                             unsigned top_delta) {
     PLONK_SHORT_KERNEL();
@@ -722,7 +722,7 @@ __global__ void __launch_bounds__(256) msm_comb_slow_kernel(const G1Affine* look
                 pt.x = fp_load(&src->x);
                 pt.y = fp_load(&src->y);
                 if (d >> 31) pt.y = fp_neg(pt.y);
-                g1_madd<true>(acc, pt);
+                g1_madd<false>(acc, pt);  // the rare branch inline: the out-of-line g1_madd_equal_x alone holds 97 VGPRs, one more than fit
             }
         }
         msm_fold_store(red, acc, tid, 256, m, out_xy, flags);

@@ -70,8 +70,10 @@ __global__ void li_coset_kernel(const Fr* xs, const Fr* roots, size_t n4, size_t
 // ------------------------------------------------------------------------------------------------
 // One transcript round of every proof (transcript_device.h): the round's commitments, or evaluations, are staged big-endian in
 // sh.msg; an identity commitment (flag set) is absorbed as zeros and reported through `error`.
+// Round 0 also opens the batch's failure flags: it zeroes the proof's word of gate_fail (plonk_prover::Rounds::closes + B), which
+// gate_check_kernel, the next kernel on the stream, ORs into — one dispatch fewer per batch than a memset in between.
 __global__ void __launch_bounds__(2 * TC_LANES) transcript_kernel(int round, ProofState* st, size_t B, const Fq* commit_xy,
-                                                                  const uint8_t* flags, ChallengeConsts cc) {
+                                                                  const uint8_t* flags, ChallengeConsts cc, uint32_t* gate_fail) {
     PLONK_SHORT_KERNEL();
     __shared__ TcShared shared[2];
     const unsigned grp = threadIdx.x / TC_LANES, lane = threadIdx.x % TC_LANES;
@@ -107,7 +109,10 @@ __global__ void __launch_bounds__(2 * TC_LANES) transcript_kernel(int round, Pro
     // `error` was raised by the lanes that staged a flagged coordinate
     if (error) s.error = 1;
     if (lane == 0) {
-        if (round == 0) s.error = 0;
+        if (round == 0) {
+            s.error = 0;
+            gate_fail[b] = 0;  // gate_check_kernel, next on the stream, only ever ORs into the word
+        }
         if (round == 1) { s.beta = c0; s.gamma = c1; }
         if (round == 2) { s.alpha = c0; s.fft_cofactor = c1; }
         if (round == 3) s.zeta = c0;
@@ -129,7 +134,7 @@ struct QuotientIn { const Fr* wit[5]; const Fr* fixed[FX_COUNT]; const Fr* l0; c
 // four products share two reductions (fpl_mul_add), sums of two are multiplied as they stand and only the seven sums of three
 // or more are carry-swept: ~4 800 instructions per point against ~5 800 on packed residues.  Bounds, in units of m, beside
 // each line ("n" = normalised: limbs 0..7 in [0, 2^29)); the emulator build asserts them on every operand.
-__global__ void __launch_bounds__(256) quotient_kernel(QuotientIn in, ZhInv zh, const ProofState* st, RoundChallenges direct, unsigned n4, Fr* quot,
+__global__ void PLONK_BESIDE_ACC(256, 64) quotient_kernel(QuotientIn in, ZhInv zh, const ProofState* st, RoundChallenges direct, unsigned n4, Fr* quot,
                                                        unsigned coset_log, unsigned out_stride) {
     PLONK_WORK_KERNEL();
     typedef FpL<FrParams> L;
@@ -437,7 +442,7 @@ static int ensure_rounds(plonk_prover* p, size_t B) { return ensure_buffers(p, B
 // One transcript round of every proof: round 0 opens the transcripts, round r absorbs what round r of the prover produced.
 static void transcript_round(plonk_prover* p, size_t B, int round) {
     PLONK_LAUNCH(transcript_kernel, dim3((unsigned)((B + 1) / 2)), dim3(2 * TC_LANES), 0, p->circuit.ctx->stream, round, p->results.state, B,
-                 (const Fq*)p->results.commit_xy, (const uint8_t*)p->results.commit_flags, p->circuit.chal);
+                 (const Fq*)p->results.commit_xy, (const uint8_t*)p->results.commit_flags, p->circuit.chal, p->rounds.closes + B);
 }
 
 // `count` x B commitments into the proof records' points from `first_point` on: of the Lagrange values under the Lagrange-basis
@@ -708,7 +713,6 @@ int plonk_prover_run(plonk_prover* p, size_t B) {
 
     transcript_round(p, B, 0);
     // ---- round 1: coefficient forms of A, B, C, PI; commit A, B, C            prover.py:86-119
-    PLONK_CHECK_HIP(hipMemsetAsync(r.closes + B, 0, B * sizeof(uint32_t), s));
     PLONK_LAUNCH(gate_check_kernel, grid1(B * n), dim3(256), 0, s, (const Fr*)r.wit_lag, pub, c.n_public,
                  c.sparse_pi ? (const Fr*)nullptr : (const Fr*)(r.wit_lag + 3 * B * n), (const Fr*)c.fixed_lag, cid, n, B, r.closes + B);  // prover.py:108-116
     if (c.sparse_pi) {

@@ -4,6 +4,7 @@
 // written once, and the host reaches them through scan_grand_product / scan_evaluations / scan_divisions, which take S.
 #pragma once
 #include "prover.h"
+#include "wave.h"  // wave_lane_xor: the evaluations' sums inside a wave
 
 #define SCAN_THREADS 256  // lanes of every workgroup in this file
 
@@ -130,52 +131,96 @@ __global__ void PLONK_BESIDE_ACC(SCAN_THREADS, 4) grand_product_kernel(GrandProd
 
 // ------------------------------------------------------------------------------------------------
 // Round 4 (prover.py:228-239): evaluate coefficient forms at zeta (and Z at zeta*w): lane t Horner-evaluates its chunk of each
-// polynomial, scales by x^(chunk start) and the workgroup tree-reduces.  polys: Ac, Bc, Cc, S1c, S2c at zeta; Zc at zeta*w; PIc
-// at zeta.  Leaves the seven sums over the workgroup's rows in red[p][0].  fixed_coef: [K][8][n], proof b is of circuit cid[b]
-// (cid == null: circuit 0).
-PLONK_DEV void eval_chunk_sums(Fr (*red)[SCAN_THREADS], const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr& zeta, const Fr& zeta_w,
-                               size_t b, size_t n, size_t B, const LaneRange& r, unsigned tid) {
-    if (cid) fixed_coef += (size_t)cid[b] * FX_COUNT * n;
-    const Fr* polys[NEVAL] = {coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
-                              fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (4 * B + b) * n,
-                              coef + (3 * B + b) * n};
-    // x^(chunk start) once per evaluation point, not once per polynomial
-    const Fr shift_z = fp_pow_u64(zeta, (uint64_t)r.lo), shift_zw = fp_pow_u64(zeta_w, (uint64_t)r.lo);
-    // Horner on lazy limbs (fpl.h), the seven chains side by side: acc x is normalised in (-m, 2m), plus a coefficient it is a
-    // sum of two — a valid multiplicand as it stands; the evaluation points sit in scalar registers
+// polynomial, scales by x^(chunk start) and the workgroup adds the lanes' values up.  polys: Ac, Bc, Cc, S1c, S2c at zeta; Zc at
+// zeta*w; PIc at zeta.  fixed_coef: [K][8][n], proof b is of circuit cid[b] (cid == null: circuit 0).
+//
+// The lane walks its rows once per PASS, a pass holding the chains of one evaluation point that fit in the 96 registers free
+// beside the MSM accumulation (PLONK_BESIDE_ACC): {Z} at zeta*w, then {A, B, C} and {S1, S2, PI} at zeta.  Seven chains at once were 63
+// accumulator registers beside the multiplication's temporaries (242 VGPRs).  Each sum is then reduced on its packed canonical
+// value: inside the wave through wave_lane_xor (six steps, no LDS, no barrier), and the waves' values through wsum[wave][sum] —
+// 896 bytes of LDS and one barrier where the tree over red[7][256] took 56 KB and nine.  Field addition is exact and every value
+// canonical, so the order of the additions changes no bit of a sum.
+#define EVAL_WAVES (SCAN_THREADS / 64)
+struct EvalWaveSums { Fr v[EVAL_WAVES][NEVAL]; };
+
+// all 64 lanes of the wave must call this together: afterwards every lane holds the wave's sum
+PLONK_DEV Fr fr_wave_sum(Fr v, unsigned lane) {
+    const auto step = [&](auto M_) PLONK_LAMBDA_INLINE {
+        constexpr unsigned MASK = decltype(M_)::value;
+        Fr o;
+#pragma unroll
+        for (int i = 0; i < 8; i++) o.v[i] = wave_lane_xor<MASK>(v.v[i], lane);
+        v = fp_add(v, o);
+    };
+    step(WaveIdx<32>{});
+    step(WaveIdx<16>{});
+    step(WaveIdx<8>{});
+    step(WaveIdx<4>{});
+    step(WaveIdx<2>{});
+    step(WaveIdx<1>{});
+    return v;
+}
+
+// One pass: the chains polys[K0 .. K0 + NK) over the lane's rows at the point x (limbs xl, in scalar registers), scaled by
+// shift = x^(chunk start); the wave's sum of chain K0 + k goes to ws.v[wave][slot[K0 + k]].
+template <unsigned K0, unsigned NK>
+PLONK_DEV void eval_pass(EvalWaveSums& ws, const Fr* const (&polys)[NEVAL], const unsigned (&slot)[NEVAL], const FpL<FrParams>& xl, const Fr& shift,
+                         const LaneRange& r, unsigned tid) {
     typedef FpL<FrParams> L;
-    const L zl = fpl_from_fp_uniform(zeta), zwl = fpl_from_fp_uniform(zeta_w);
-    L acc[NEVAL];
-    wave_for<NEVAL>([&](auto P_) { acc[decltype(P_)::value] = fpl_zero<FrParams>(); });
+    // Horner on lazy limbs (fpl.h), the pass's chains side by side: acc x is normalised in (-m, 2m), plus a coefficient it is a
+    // sum of two — a valid multiplicand as it stands
+    L acc[NK];
+    wave_for<NK>([&](auto K_) { acc[decltype(K_)::value] = fpl_zero<FrParams>(); });
 #pragma unroll 1
     for (size_t i = r.hi; i-- > r.lo;)
-        wave_for<NEVAL>([&](auto P_) {
-            constexpr unsigned p = decltype(P_)::value;
-            acc[p] = fpl_add(fpl_mul(acc[p], p == 5 ? zwl : zl), fpl_from_fp(fp_load(polys[p] + i)));  // (-m, 3m), limbs < 2^30
+        wave_for<NK>([&](auto K_) {
+            constexpr unsigned k = decltype(K_)::value;
+            acc[k] = fpl_add(fpl_mul(acc[k], xl), fpl_from_fp(fp_load(polys[K0 + k] + i)));  // (-m, 3m), limbs < 2^30
         });
-    const L sh_z = fpl_from_fp(shift_z), sh_zw = fpl_from_fp(shift_zw);
-    wave_for<NEVAL>([&](auto P_) {
-        constexpr unsigned p = decltype(P_)::value;
-        red[p][tid] = r.lo < r.hi ? fpl_pack_canonical(fpl_mul(acc[p], p == 5 ? sh_zw : sh_z)) : fp_zero<FrParams>();
+    const L sh = fpl_from_fp(shift);
+    const unsigned wave = tid / 64, lane = tid % 64;
+    wave_for<NK>([&](auto K_) {
+        constexpr unsigned k = decltype(K_)::value;
+        const Fr mine = r.lo < r.hi ? fpl_pack_canonical(fpl_mul(acc[k], sh)) : fp_zero<FrParams>();  // an empty lane adds zero
+        const Fr sum = fr_wave_sum(mine, lane);
+        if (lane == 0) ws.v[wave][slot[K0 + k]] = sum;
     });
+    PLONK_SCHED_FENCE();  // the next pass starts with this one's registers free
+}
+
+// Returns, in lane p < NEVAL, sum p over the workgroup's rows (the other lanes: nothing of use).  All lanes must call it.
+PLONK_DEV Fr eval_chunk_sums(EvalWaveSums& ws, const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, const Fr& zeta, const Fr& zeta_w,
+                             size_t b, size_t n, size_t B, const LaneRange& r, unsigned tid) {
+    if (cid) fixed_coef += (size_t)cid[b] * FX_COUNT * n;
+    // in pass order; slot[k]: the place of chain k among the seven sums (Zc is sum 5, PIc sum 6)
+    const Fr* const polys[NEVAL] = {coef + (4 * B + b) * n, coef + (0 * B + b) * n, coef + (1 * B + b) * n, coef + (2 * B + b) * n,
+                                    fixed_coef + FX_S1 * n,  fixed_coef + FX_S2 * n,  coef + (3 * B + b) * n};
+    const unsigned slot[NEVAL] = {5, 0, 1, 2, 3, 4, 6};
+    // x^(chunk start) once per evaluation point and lane, before the passes: not once per polynomial, nor once per pass
+    const Fr shift_z = fp_pow_u64(zeta, (uint64_t)r.lo), shift_zw = fp_pow_u64(zeta_w, (uint64_t)r.lo);
+    // Zc first: its chunk power is then out of the way of the two passes of three chains
+    eval_pass<0, 1>(ws, polys, slot, fpl_from_fp_uniform(zeta_w), shift_zw, r, tid);
+    eval_pass<1, 3>(ws, polys, slot, fpl_from_fp_uniform(zeta), shift_z, r, tid);
+    eval_pass<4, 3>(ws, polys, slot, fpl_from_fp_uniform(zeta), shift_z, r, tid);
     __syncthreads();
-    for (unsigned s = SCAN_THREADS / 2; s > 0; s >>= 1) {  // the seven sums share the barriers
-        if (tid < s)
-            for (int p = 0; p < NEVAL; p++) red[p][tid] = fp_add(red[p][tid], red[p][tid + s]);
-        __syncthreads();
+    Fr total = fp_zero<FrParams>();
+    if (tid < NEVAL) {
+        total = ws.v[0][tid];
+        for (unsigned wv = 1; wv < EVAL_WAVES; wv++) total = fp_add(total, ws.v[wv][tid]);
     }
+    return total;
 }
 
 // One workgroup per proof.
-__global__ void __launch_bounds__(SCAN_THREADS) eval_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, ProofState* st,
+__global__ void PLONK_BESIDE_ACC(SCAN_THREADS, 8) eval_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, ProofState* st,
                                                             size_t n, size_t B) {
     PLONK_SHORT_KERNEL();
-    __shared__ Fr red[NEVAL][SCAN_THREADS];
+    __shared__ EvalWaveSums ws;
     const size_t b = blockIdx.x;
     const unsigned tid = threadIdx.x;
     const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    eval_chunk_sums(red, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, block_lane_range(n, tid), tid);
-    if (tid < NEVAL) st[b].evals[tid] = red[tid][0];
+    const Fr total = eval_chunk_sums(ws, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, block_lane_range(n, tid), tid);
+    if (tid < NEVAL) st[b].evals[tid] = total;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -315,15 +360,15 @@ __global__ void __launch_bounds__(SCAN_THREADS) gp_seg_apply_kernel(size_t n, co
 
 // Evaluations, launch 1 of 2, grid (S, B): the blocked Horner over the segment's rows, every lane's chains scaled by x^(global
 // chunk start); the segment's seven sums go to part[b][s][NEVAL].
-__global__ void __launch_bounds__(SCAN_THREADS) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, const ProofState* st,
+__global__ void PLONK_BESIDE_ACC(SCAN_THREADS, 8) eval_seg_kernel(const Fr* coef, const Fr* fixed_coef, const uint32_t* cid, Fr w, const ProofState* st,
                                                                 size_t n, size_t B, Fr* part) {
     PLONK_SHORT_KERNEL();
-    __shared__ Fr red[NEVAL][SCAN_THREADS];
+    __shared__ EvalWaveSums ws;
     const size_t b = blockIdx.y;
     const unsigned tid = threadIdx.x, S = gridDim.x;
     const Fr zeta = st[b].zeta, zeta_w = fp_mul(zeta, w);
-    eval_chunk_sums(red, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, seg_lane_range(n, S, blockIdx.x, tid), tid);
-    if (tid < NEVAL) fp_store(part + (b * S + blockIdx.x) * NEVAL + tid, red[tid][0]);
+    const Fr total = eval_chunk_sums(ws, coef, fixed_coef, cid, zeta, zeta_w, b, n, B, seg_lane_range(n, S, blockIdx.x, tid), tid);
+    if (tid < NEVAL) fp_store(part + (b * S + blockIdx.x) * NEVAL + tid, total);
 }
 
 // Launch 2 of 2, one workgroup per proof: lane group p (32 lanes) adds the S partial sums of evaluation p into st[b].evals[p].
